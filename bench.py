@@ -16,10 +16,14 @@ N GPUs:       python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
 
 Every timed step is a full learner step (all envs act, every env's TD error
 is back-propagated, the optimizer updates all parameters); nothing is skipped.
-After the timed window (untimed) every env plays one complete 5,846-step episode
-with the policy being learned and one with a uniformly random policy: the
-"episode return" half of the metric (final portfolio - budget, mean / std over
-all envs of all ranks).  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line.  With ``--full``, after the timed window (untimed) every env also plays
+one complete 5,846-step episode with the policy being learned and one with a
+uniformly random policy: the "episode return" half of the metric (final
+portfolio - budget, mean / std over all envs of all ranks), followed by the
+stabilised learner's evaluation and (N > 1) the raw all-reduce latency.
+``--dump-outputs DIR`` writes what the last timed step left behind as
+``DIR/<name>.npy``.  Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -72,6 +76,55 @@ def stable_learner_eval(args, dev, rank, world, group, train_steps):
     return res
 
 
+def ensure_native() -> None:
+    """The in-tree native build (a no-op when up to date).  A tree that this user cannot write -- built by
+    another user, or mounted read-only -- cannot even take the build lock: there the libraries already built
+    are run as they are, provided they exist and no source is newer than them; anything else stays an error."""
+    import glob
+
+    import build as _build
+
+    try:
+        _build.build_all()
+    except PermissionError:
+        hip = glob.glob(os.path.join(_build.CSRC, "*.hip")) + glob.glob(os.path.join(_build.CSRC, "*.h"))
+        rt = glob.glob(os.path.join(_build.CSRC, "runtime", "*"))
+        if _build._newer(_build.HIP_LIB, hip) or _build._newer(_build.RT_LIB, rt):
+            raise
+        print("bench.py: the tree is not writable; running the native libraries already built", file=sys.stderr)
+
+
+def snapshot_outputs(eng):
+    """What a caller of the timed path holds after its last step (device copies, taken right after the timed
+    window): the updated parameters, every env's action and reward of that step, its budget / shares / last
+    trade price and portfolio after it, and the step statistics accumulated so far."""
+    st = eng.state
+    out = {"params": eng.params, "budget": st.budget, "shares": st.shares, "value": st.value,
+           "portfolios": eng.current_portfolios()}
+    if eng.backend == "native":
+        out.update(actions=eng.actions_out, rewards=eng.rewards_out, stat_acc=eng.stat_acc)
+    return {k: v.detach().clone() for k, v in out.items()}
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all
+
+
+def write_outputs(snap, out_dir: str) -> None:
+    """``out_dir/<name>.npy``, float32 (float64 for float64 tensors); an array over its share of DUMP_BYTES is
+    cut to a fixed, seeded sample of its elements (the same elements on every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(snap))
+    for name, t in snap.items():
+        a = t.cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32).reshape(-1)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,8 +157,14 @@ def main() -> int:
     ap.add_argument("--pg-timeout", type=float, default=300.0,
                     help="N>1: collective timeout (s); with TORCH_NCCL_ASYNC_ERROR_HANDLING=1 a dead peer fails "
                          "the job instead of hanging it")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also run the untimed evaluations: the full-episode returns, the "
+                         "stabilised learner and (N>1) the all-reduce latency (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (parameters, per-env actions, "
+                         "rewards, budget, shares, trade price, portfolio; step statistics) as DIR/<name>.npy")
     ap.add_argument("--no-episode", action="store_true",
-                    help="skip the untimed full-episode returns after the timed window (greedy learned policy, "
+                    help="--full: skip the untimed full-episode returns after the timed window (greedy learned policy, "
                          "greedy random-init policy, buy-and-hold, online learned episode, random policy)")
     ap.add_argument("--target-every", type=int, default=0,
                     help="learning knob: target network refreshed every N steps (csrc/qtarget.hip pass per step)")
@@ -113,18 +172,18 @@ def main() -> int:
     ap.add_argument("--reward-scale", type=float, default=1.0, help="learning knob: reward multiplier in the TD target")
     ap.add_argument("--ramp-mode", default="position", help="learning knob: exploit ramp over 'position' | 'global'")
     ap.add_argument("--no-stable-eval", action="store_true",
-                    help="skip the untimed evaluation of the stabilised learner (preset flagship_stable: target net + "
+                    help="--full: skip the untimed evaluation of the stabilised learner (preset flagship_stable: target net + "
                          "Double DQN, trained for the same number of steps on the same banks)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_episode = args.no_stable_eval = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # native build BEFORE any process group exists (build.build_all serialises concurrent builders
     # with a file lock): no rank waits in a collective while another compiles
-    import build as _build  # in-tree native build (no-op when up to date)
-
-    _build.build_all()
+    ensure_native()
     if not torch.cuda.is_available():
         print("bench.py needs a GPU", file=sys.stderr)
         return 2
@@ -203,6 +262,9 @@ def main() -> int:
         prof.__exit__(None, None, None)
         prof.export_chrome_trace(args.trace)
     eng.check_kernel_err()   # (untimed) a ws ring-protocol abort in the window would make its gradients invalid
+    if args.dump_outputs:
+        write_outputs(snapshot_outputs(eng), os.path.join(args.dump_outputs, f"rank{rank}") if world > 1
+                      else args.dump_outputs)
     trained_steps = eng.step_count   # prime + warm-up + timed: what the evaluated policy has learned from
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=dev)
     pf1 = eng.current_portfolios().double()
@@ -217,7 +279,7 @@ def main() -> int:
         dist.all_reduce(stats)
     el = float(elapsed[0])
     allreduce_ms = None
-    if world > 1 and eng._sync is not None:
+    if args.full and world > 1 and eng._sync is not None:
         # latency of the gradient all-reduce (same size, same group), measured AFTER the timed window
         scratch = torch.zeros_like(eng.params)
         eng._sync.enable_timing()

@@ -1,7 +1,9 @@
 """End-to-end ShareTradeHelper runs (CPU): price service -> router -> workers -> learner.
 
 The MSFT series comes from ``config.default_csv_path()``: the reference checkout's CSV when present,
-else the bundled parsed copy (``sharetrade/data/msft_prices.npz``), so these parity runs never skip."""
+else the bundled parsed copy (``sharetrade/data/msft_prices.npz``), so these parity runs never skip.
+The reference's CSV itself is stored as ``tests/golden/MSFT-stock-prices-revised.txt``: the bundled copy
+is re-derived from it on every machine."""
 import json
 import os
 import subprocess
@@ -12,9 +14,10 @@ import numpy as np
 import pytest
 import torch
 
-from sharetrade.config import BUNDLED_SERIES, REFERENCE_CSV, default_csv_path, preset_config
+from sharetrade.config import BUNDLED_SERIES, default_csv_path, preset_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN_CSV = os.path.join(ROOT, "tests", "golden", "MSFT-stock-prices-revised.txt")
 
 
 def _cfg(max_ok=True):
@@ -30,16 +33,13 @@ def test_bundled_series_is_the_reference_csv():
 
     z = np.load(BUNDLED_SERIES)
     assert len(z["days"]) == 6047 and np.all(np.diff(z["days"]) > 0)
-    if not os.path.exists(REFERENCE_CSV):
-        pytest.skip(f"PARITY SOURCE UNCHECKED: {REFERENCE_CSV} is absent here, so the bundled copy "
-                    f"{BUNDLED_SERIES} (sha256 of its source {str(z['source_sha256'])[:16]}...) is not re-derived")
-    ref = load_csv(REFERENCE_CSV)
+    ref = load_csv(GOLDEN_CSV)
     dates = sorted(ref)
     assert [d.toordinal() for d in dates] == z["days"].tolist()
     assert np.array_equal(np.asarray([ref[d] for d in dates]), z["prices"])
     import hashlib
 
-    assert hashlib.sha256(open(REFERENCE_CSV, "rb").read()).hexdigest() == str(z["source_sha256"])
+    assert hashlib.sha256(open(GOLDEN_CSV, "rb").read()).hexdigest() == str(z["source_sha256"])
 
 
 @pytest.mark.parametrize("engine", ["actors", "vector"])

@@ -68,9 +68,12 @@ def test_test_profile(tmp_path):
     assert cfg.persist.journal_plugin == "inmemory" and cfg.log.loglevel == "DEBUG" and cfg.log.test_listener
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="reference checkout not mounted")
+GOLDEN_CONF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_conf")
+
+
 def test_reference_conf_files_parse():
-    for f in ("src/main/resources/application.conf", "src/test/resources/application.conf"):
-        with open(os.path.join("/root/reference", f)) as fh:
+    """The reference's two application.conf files (main and test resources), stored under tests/golden/."""
+    for f in ("main_application.conf", "test_application.conf"):
+        with open(os.path.join(GOLDEN_CONF, f)) as fh:
             d, _ = hocon.akka_to_config(hocon.loads(fh.read()))
         assert d["persist"]["journal_plugin"] in ("file", "inmemory")

@@ -19,5 +19,5 @@ for E in 262144 524288; do
 done
 timeout -k 10 300 python -u -m pytest -x -q --timeout 200 --timeout-method thread tests/test_gpu_bench.py > $O/pytest_bench.log 2>&1 || { tail -30 $O/pytest_bench.log; exit 1; }
 tail -2 $O/pytest_bench.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python -c "import json;d=json.load(open('$O/bench.json'));e=d['episode_return'];print(d['ms_per_step'], {k:e[k] for k in ('greedy_median','random_median','buy_hold_median')}, e['stable_learner'])"
