@@ -116,34 +116,10 @@ static_assert(NJW == 7 && NJOB <= 6 * 64 + 32, "wave 7 stages the env rows into 
 constexpr int CTL_TAIL = 0, CTL_DQ = 4, CTL_ABORT = 12;
 constexpr int SPIN_LIMIT = 1 << 22;
 
-// input slot -> flat-layout column of W0^T (the permutation of qstep_ws.hip: the last 16-wide k-step puts
-// budget, shares, the constant 1 and the window's last price in lane group 0)
-ST_DEV int slot_col(int s) {
-  if (s < 192) return s;
-  const int t = s - 192, g = t >> 2, j = t & 3;
-  if (g == 0) return j < 3 ? 201 + j : 200;
-  if (g == 1) return 192 + j;
-  if (g == 2) return 196 + j;
-  return 204 + j;
-}
-
 // W1^T image: 16-byte unit c / 8 of row r at (c / 8) ^ (r & 15): the dZ1 B-fragment reads (16 rows, one unit
 // each) hit 16 different bank groups
 ST_DEV int w1t_off(int r, int c) { return r * HP + ((((c >> 3) ^ (r & 15))) << 3) + (c & 7); }
 
-ST_DEV s4v zero_s4() { s4v z = {0, 0, 0, 0}; return z; }
-ST_DEV s8v cat8(s4v a, s4v b) {
-  s8v r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
-  r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-  return r;
-}
-ST_DEV s4v pk4(float a, float b, float c, float d) {
-  uint2 v;
-  v.x = pack_bf2(a, b);
-  v.y = pack_bf2(c, d);
-  return __builtin_bit_cast(s4v, v);
-}
 ST_DEV s8v pk8(const float* v) {
   uint4 r;
   r.x = pack_bf2(v[0], v[1]);
@@ -152,33 +128,7 @@ ST_DEV s8v pk8(const float* v) {
   r.w = pack_bf2(v[6], v[7]);
   return __builtin_bit_cast(s8v, r);
 }
-typedef short s2v __attribute__((ext_vector_type(2)));
-// relu then bf16 == bf16 then relu on the bits (a negative bf16 is a negative int16)
-ST_DEV s4v relu_bf(f4v v) {
-  const s2v z = {0, 0};
-  const s2v a = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[0], v[1])), z);
-  const s2v b = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[2], v[3])), z);
-  s4v r = {a[0], a[1], b[0], b[1]};
-  return r;
-}
-// bf16(v) * [act > 0] on packed integers (act: relu'd bf16 bits, >= 0): bits * min(act, 1)
-ST_DEV unsigned mask2(unsigned x, unsigned act) {
-  unsigned m, r;
-  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(act), "v"(0x00010001u));
-  asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
-  return r;
-}
-ST_DEV s4v mask_pk(f4v v, s4v act) {
-  const uint2 a = __builtin_bit_cast(uint2, act);
-  uint2 r;
-  r.x = mask2(pack_bf2(v[0], v[1]), a.x);
-  r.y = mask2(pack_bf2(v[2], v[3]), a.y);
-  return __builtin_bit_cast(s4v, r);
-}
 ST_DEV f4v ld_f4(const void* p) { return *reinterpret_cast<const f4v*>(p); }
-ST_DEV int lds_acq(const int* w) {
-  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
 // LDS-DMA from inline asm (csrc/qserve.hip): the builtin makes hipcc order every later LDS store behind the
 // DMA; the kernel retires it itself (s_waitcnt vmcnt(0) before the phase's barrier).  lds_off: wave-uniform
 // byte offset of the wave-instruction's destination (lane i lands at lds_off + 16 i / 4 i).
@@ -236,12 +186,9 @@ __global__ void __launch_bounds__(NT, 1) qstep_pipe_kernel(QStepParams p) {
     // packed u1 (24 bits) | random action << 30, into the env's action row until the env step replaces it
     for (int i = tid; i < nmy * C; i += NT) {
       const int e = ((int)blockIdx.x + (i / C) * (int)gridDim.x) * C + (i % C);
-      uint32_t c0 = (uint32_t)(p.env_offset + e), c1 = (uint32_t)(step & 0xFFFFFFFFull),
-               c2 = (uint32_t)(step >> 32), c3 = 0u;
-      philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-      int rnd = (int)(u24(c1) * 3.0f);
-      rnd = rnd > 2 ? 2 : rnd;
-      p.env[(size_t)ER_ACTION * p.E + e] = (int)((c0 >> 8) | ((uint32_t)rnd << 30));
+      uint32_t r1, r2;
+      policy_bits((uint32_t)(p.env_offset + e), step, p.key0, p.key1, r1, r2);
+      p.env[(size_t)ER_ACTION * p.E + e] = (int)((r1 >> 8) | ((uint32_t)random_action(u24(r2)) << 30));
     }
     wait_vm0();          // the draws are read back (by LDS-DMA) by other waves of this workgroup
   }
@@ -465,14 +412,12 @@ __global__ void __launch_bounds__(NT, 1) qstep_pipe_kernel(QStepParams p) {
         greedy = q2 > best ? 2 : greedy;
         const float u1 = (float)(rw & 0xFFFFFF) * (1.0f / 16777216.0f);
         const int rnd = (int)((unsigned)rw >> 30);
-        exploit = u1 < fminf(p.eps, __fmul_rn((float)pos, p.inv_ramp));
+        exploit = exploits(u1, p.eps, (float)pos, p.inv_ramp);
         act = exploit ? greedy : rnd;
-        const float bd = p.compat_env ? p.b0 : bud0;
-        const int sd = p.compat_env ? p.s0 : sh0;
-        const bool buy = (act == 0) && (bd >= vnew_e);
-        const bool sell = (act == 1) && (sd > 0);
-        b2 = buy ? __fsub_rn(bd, vnew_e) : (sell ? __fadd_rn(bd, vnew_e) : bd);
-        s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
+        const Holding h2 = trade(act, trade_base(bud0, sh0, p.compat_env, p.b0, p.s0), vnew_e);
+        b2 = h2.budget;
+        s2 = h2.shares;
+        // (reward of trade_rule.h with the return as a select: the call's branch changes this kernel's SGPR spills)
         const float cur = __fadd_rn(bud0, __fmul_rn((float)sh0, vprev));
         const float nw = __fadd_rn(b2, __fmul_rn((float)s2, vnew_e));
         rew = __fsub_rn(nw, cur);
@@ -506,8 +451,9 @@ __global__ void __launch_bounds__(NT, 1) qstep_pipe_kernel(QStepParams p) {
         const int ts2 = r1.z, tact = r1.w & 255;
         const bool tdone = (r1.w >> 8) != 0;
         dslot = p.target_compat ? am : tact;
-        const float y = __fadd_rn(trew, __fmul_rn(p.gamma, mx));
+        const float y = td_target(trew, 1.0f, p.gamma, mx);
         qs = dslot == 0 ? tq0 : (dslot == 1 ? tq1 : tq2);
+        // (td_dq of trade_rule.h, kept select-only with the argmaxes above: no branch splits this phase's region)
         diff = __fsub_rn(qs, y);
         float dq = p.loss_coef * fminf(fmaxf(diff, -clip), clip);
         dq = (p.output_relu && !(qs > 0.f)) || !v2 ? 0.f : dq;

@@ -8,6 +8,7 @@
 // action, reward, budget', shares', done} = 36 B -> 36 MB for 1M transitions; states
 // are rebuilt by deep_gather directly into the bf16 GEMM operand (Hankel addressing).
 #include "common.h"
+#include "trade_rule.h"
 
 namespace st {
 
@@ -196,24 +197,18 @@ struct DeepEnv {
 // epsilon-greedy + Buy/Sell/Hold transition + replay insert of env e (greedy: argmax of its Q row)
 ST_DEV void deep_env_one(const DeepEnv& p, int e, int greedy, unsigned long long step, float& r_, float& x_) {
   const int ps = p.pos[e];
-  uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(step & 0xFFFFFFFFull), c2 = (uint32_t)(step >> 32), c3 = 0u;
-  philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-  const float u1 = u24(c0), u2 = u24(c1);
-  const bool exploit = u1 < fminf(p.eps, (float)ps * p.inv_ramp);
-  int rnd = (int)(u2 * 3.0f);
-  rnd = rnd > 2 ? 2 : rnd;
-  const int a = exploit ? greedy : rnd;
+  float u1, u2;
+  policy_draw((uint32_t)e, step, p.key0, p.key1, u1, u2);
+  const bool exploit = exploits(u1, p.eps, (float)ps, p.inv_ramp);
+  const int a = exploit ? greedy : random_action(u2);
   const float* pr = p.prices + (size_t)e * p.T + ps;
   const float vnew = pr[p.H];
   const float b = p.budget[e], vprev = p.value[e];
   const int s = p.shares[e];
-  const float bd = p.compat_env ? p.b0 : b;
-  const int sd = p.compat_env ? p.s0 : s;
-  const bool buy = (a == 0) && (bd >= vnew);
-  const bool sell = (a == 1) && (sd > 0);
-  const float b2 = buy ? bd - vnew : (sell ? bd + vnew : bd);
-  const int s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
-  const float rew = (b2 + (float)s2 * vnew) - (b + (float)s * vprev);
+  const Holding h2 = trade(a, trade_base(b, s, p.compat_env, p.b0, p.s0), vnew);
+  const float b2 = h2.budget;
+  const int s2 = h2.shares;
+  const float rew = reward(b, s, vprev, b2, s2, vnew, 0);
   const int np = ps + 1;
   const bool done = np >= p.T - p.H;
   // replay insert (ring)

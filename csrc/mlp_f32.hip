@@ -20,6 +20,7 @@
 // >93% padding.  Weights are the flat fp32 layout of sharetrade/models/qnet.py
 // (W^T[out_p][in_p] row-major; layer-0 bias folded into column `bias_col`).
 #include "common.h"
+#include "trade_rule.h"
 
 namespace st {
 
@@ -121,8 +122,6 @@ ST_DEV void forward_row(const F32Net& net, const float* __restrict__ P, float* a
   }
 }
 
-ST_DEV float feat_p(float w, float inv, int mode) { return mode ? __fsub_rn(__fmul_rn(w, inv), 1.0f) : w; }
-
 __global__ void __launch_bounds__(F_NT) f32_rows_kernel(F32Net net, F32Rows r) {
   // LDS: two activation stacks (x and x') + q buffers + dz scratch
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -159,12 +158,12 @@ __global__ void __launch_bounds__(F_NT) f32_rows_kernel(F32Net net, F32Rows r) {
     for (int k = tid; k < in_p; k += F_NT) {
       float v = 0.f, vn = 0.f;
       if (k < r.H) {
-        v = feat_p(pr[k], inv, r.feat_mode);
-        vn = feat_p(pr[k + 1], invn, r.feat_mode);
+        v = feat_price(pr[k], inv, r.feat_mode);
+        vn = feat_price(pr[k + 1], invn, r.feat_mode);
       } else if (k == r.H) {
-        v = r.feat_mode ? __fmul_rn(b, r.inv_b0) : b;
+        v = feat_budget(b, r.inv_b0, r.feat_mode);
       } else if (k == r.H + 1) {
-        v = r.feat_mode ? __fmul_rn(__fmul_rn((float)s, last), r.inv_b0) : (float)s;
+        v = feat_shares(s, last, r.inv_b0, r.feat_mode);
       } else if (k == net.bias_col) {
         v = 1.f;
         vn = 1.f;
@@ -197,38 +196,23 @@ __global__ void __launch_bounds__(F_NT) f32_rows_kernel(F32Net net, F32Rows r) {
       const int e = row;
       const unsigned long long step = r.ctrl[0];
       const float q0 = Q[0], q1 = Q[1], q2 = Q[2];
-      int greedy = 0;
-      float best = q0;
-      if (q1 > best) { best = q1; greedy = 1; }
-      if (q2 > best) { best = q2; greedy = 2; }
       const int ps = s_envi[0];
-      uint32_t c0 = (uint32_t)(r.env_offset + e), c1 = (uint32_t)(step & 0xFFFFFFFFull),
-               c2 = (uint32_t)(step >> 32), c3 = 0u;
-      philox4x32(c0, c1, c2, c3, r.key0, r.key1);
-      const float u1 = u24(c0), u2 = u24(c1);
-      const bool exploit = u1 < fminf(r.eps, __fmul_rn((float)ps, r.inv_ramp));
-      int rnd = (int)(u2 * 3.0f);
-      rnd = rnd > 2 ? 2 : rnd;
-      const int a = exploit ? greedy : rnd;
+      float u1, u2;
+      policy_draw((uint32_t)(r.env_offset + e), step, r.key0, r.key1, u1, u2);
+      const int greedy = argmax3(q0, q1, q2), rnd = random_action(u2);
+      const int a = exploits(u1, r.eps, (float)ps, r.inv_ramp) ? greedy : rnd;
       const float b = s_env[0], vprev = s_env[1], vnew = s_env[2];
       const int s = s_envi[1];
-      const float bd = r.compat_env ? r.b0 : b;
-      const int sd = r.compat_env ? r.s0 : s;
-      const bool buy = (a == 0) && (bd >= vnew);
-      const bool sell = (a == 1) && (sd > 0);
-      const float b2 = buy ? __fsub_rn(bd, vnew) : (sell ? __fadd_rn(bd, vnew) : bd);
-      const int s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
-      const float cur = __fadd_rn(b, __fmul_rn((float)s, vprev));
-      const float nw = __fadd_rn(b2, __fmul_rn((float)s2, vnew));
-      float rew = __fsub_rn(nw, cur);
-      if (r.reward_mode) rew = cur > 0.f ? __fdiv_rn(rew, cur) : 0.f;
-        if (r.reward_mode == 2) rew = __fsub_rn(rew, __fmul_rn(__fmul_rn(rew, 0.5f), rew));   // growth: log1p to 2nd order
+      const Holding h2 = trade(a, trade_base(b, s, r.compat_env, r.b0, r.s0), vnew);
+      const float b2 = h2.budget;
+      const int s2 = h2.shares;
+      const float rew = reward(b, s, vprev, b2, s2, vnew, r.reward_mode);
       s_env[3] = b2;
       s_env[4] = rew;
       s_envi[1] = s2;
       s_envi[2] = a;
-      AN[r.H] = r.feat_mode ? __fmul_rn(b2, r.inv_b0) : b2;
-      AN[r.H + 1] = r.feat_mode ? __fmul_rn(__fmul_rn((float)s2, vnew), r.inv_b0) : (float)s2;
+      AN[r.H] = feat_budget(b2, r.inv_b0, r.feat_mode);
+      AN[r.H + 1] = feat_shares(s2, vnew, r.inv_b0, r.feat_mode);
       if (r.actions_out) r.actions_out[e] = a;
       if (r.rewards_out) r.rewards_out[e] = rew;
     }
@@ -238,11 +222,8 @@ __global__ void __launch_bounds__(F_NT) f32_rows_kernel(F32Net net, F32Rows r) {
   // ------------------------------------------------------------ TD target + dQ
   __shared__ int s_slot;
   if (tid == 0) {
-    const float n0 = QN[0], n1 = QN[1], n2 = QN[2];
-    int am = 0;
-    float mx = n0;
-    if (n1 > mx) { mx = n1; am = 1; }
-    if (n2 > mx) { mx = n2; am = 2; }
+    float mx, diff;
+    const int am = argmax3(QN[0], QN[1], QN[2], mx);
     int slot;
     float rew;
     if (r.mode == 2) {
@@ -252,11 +233,9 @@ __global__ void __launch_bounds__(F_NT) f32_rows_kernel(F32Net net, F32Rows r) {
       slot = r.action ? r.action[row] : am;
       rew = r.reward[row];
     }
-    const float y = __fadd_rn(rew, __fmul_rn(r.gamma, mx));
+    const float y = td_target(rew, 1.0f, r.gamma, mx);
     const float qs = Q[slot];
-    const float diff = __fsub_rn(qs, y);
-    float dq = r.coef * (r.td_clip > 0.f ? fminf(fmaxf(diff, -r.td_clip), r.td_clip) : diff);
-    if (net.output_relu && !(qs > 0.f)) dq = 0.f;
+    const float dq = td_dq(qs, y, r.coef, r.td_clip, net.output_relu, diff);
     s_slot = slot;
     D0[0] = dq;
     r.loss[row] = diff * diff;

@@ -27,6 +27,7 @@
 // the row kernel's, operation for operation (TrainerChildActor.scala:118-146; quirks behind the same
 // flags).
 #include "common.h"
+#include "trade_rule.h"
 
 namespace st {
 
@@ -331,8 +332,6 @@ struct F32Batch {
   int double_dqn, ramp_global;
 };
 
-ST_DEV float f32b_feat(float w, float inv, int mode) { return mode ? __fsub_rn(__fmul_rn(w, inv), 1.0f) : w; }
-
 // one thread per element of X / X' (the divisions are per env but cheap beside the traffic)
 // one thread per (env, 4 consecutive columns) of X / X': the window's reciprocals once per thread and
 // float4 stores (one thread per element with 64-bit index math and two IEEE divisions each ran at
@@ -353,14 +352,12 @@ __global__ void __launch_bounds__(256) f32b_gather_kernel(F32Batch r) {
     v[t] = 0.f;
     vn[t] = 0.f;
     if (k < r.H) {
-      v[t] = f32b_feat(pr[k], inv, r.feat_mode);
-      vn[t] = f32b_feat(pr[k + 1], invn, r.feat_mode);
+      v[t] = feat_price(pr[k], inv, r.feat_mode);
+      vn[t] = feat_price(pr[k + 1], invn, r.feat_mode);
     } else if (k == r.H) {
-      const float b = r.budget[e];
-      v[t] = r.feat_mode ? __fmul_rn(b, r.inv_b0) : b;
+      v[t] = feat_budget(r.budget[e], r.inv_b0, r.feat_mode);
     } else if (k == r.H + 1) {
-      const int s = r.shares[e];
-      v[t] = r.feat_mode ? __fmul_rn(__fmul_rn((float)s, last), r.inv_b0) : (float)s;
+      v[t] = feat_shares(r.shares[e], last, r.inv_b0, r.feat_mode);
     } else if (k == r.bias_col) {
       v[t] = 1.f;
       vn[t] = 1.f;
@@ -378,42 +375,27 @@ __global__ void __launch_bounds__(256) f32b_env_kernel(F32Batch r) {
   const unsigned long long step = r.ctrl[0];
   const float* q = r.Q + (size_t)e * 16;
   const float q0 = q[0], q1 = q[1], q2 = q[2];
-  int greedy = 0;
-  float best = q0;
-  if (q1 > best) { best = q1; greedy = 1; }
-  if (q2 > best) { best = q2; greedy = 2; }
   const int ps = r.pos[e];
-  uint32_t c0 = (uint32_t)(r.env_offset + e), c1 = (uint32_t)(step & 0xFFFFFFFFull), c2 = (uint32_t)(step >> 32),
-           c3 = 0u;
-  philox4x32(c0, c1, c2, c3, r.key0, r.key1);
-  const float u1 = u24(c0), u2 = u24(c1);
+  float u1, u2;
+  policy_draw((uint32_t)(r.env_offset + e), step, r.key0, r.key1, u1, u2);
   const float rpos = r.ramp_global ? (float)step : (float)ps;   // exploit ramp over the step count (global)
-  const bool exploit = u1 < fminf(r.eps, __fmul_rn(rpos, r.inv_ramp));
-  int rnd = (int)(u2 * 3.0f);
-  rnd = rnd > 2 ? 2 : rnd;
-  const int a = exploit ? greedy : rnd;
+  const int greedy = argmax3(q0, q1, q2), rnd = random_action(u2);
+  const int a = exploits(u1, r.eps, rpos, r.inv_ramp) ? greedy : rnd;
   const float* pr = r.prices + (size_t)e * r.T + ps;
   const float vnew = pr[r.H];
   const float b = r.budget[e], vprev = r.value[e];
   const int s = r.shares[e];
-  const float bd = r.compat_env ? r.b0 : b;
-  const int sd = r.compat_env ? r.s0 : s;
-  const bool buy = (a == 0) && (bd >= vnew);
-  const bool sell = (a == 1) && (sd > 0);
-  const float b2 = buy ? __fsub_rn(bd, vnew) : (sell ? __fadd_rn(bd, vnew) : bd);
-  const int s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
-  const float cur = __fadd_rn(b, __fmul_rn((float)s, vprev));
-  const float nw = __fadd_rn(b2, __fmul_rn((float)s2, vnew));
-  float rew = __fsub_rn(nw, cur);
-  if (r.reward_mode) rew = cur > 0.f ? __fdiv_rn(rew, cur) : 0.f;
-        if (r.reward_mode == 2) rew = __fsub_rn(rew, __fmul_rn(__fmul_rn(rew, 0.5f), rew));   // growth: log1p to 2nd order
+  const Holding h2 = trade(a, trade_base(b, s, r.compat_env, r.b0, r.s0), vnew);
+  const float b2 = h2.budget;
+  const int s2 = h2.shares;
+  const float rew = reward(b, s, vprev, b2, s2, vnew, r.reward_mode);
   r.s_b2[e] = b2;
   r.s_s2[e] = s2;
   r.s_rew[e] = rew;
   r.s_act[e] = a;
   float* xn = r.XN + (size_t)e * r.in_p;
-  xn[r.H] = r.feat_mode ? __fmul_rn(b2, r.inv_b0) : b2;
-  xn[r.H + 1] = r.feat_mode ? __fmul_rn(__fmul_rn((float)s2, vnew), r.inv_b0) : (float)s2;
+  xn[r.H] = feat_budget(b2, r.inv_b0, r.feat_mode);
+  xn[r.H + 1] = feat_shares(s2, vnew, r.inv_b0, r.feat_mode);
   if (r.actions_out) r.actions_out[e] = a;
   if (r.rewards_out) r.rewards_out[e] = rew;
 }
@@ -425,29 +407,22 @@ __global__ void __launch_bounds__(1024) f32b_td_kernel(F32Batch r) {
   double st_r = 0.0, st_l = 0.0;
   if (e < r.E) {
   const float* qn = r.QN + (size_t)e * 16;
-  const float n0 = qn[0], n1 = qn[1], n2 = qn[2];
-  int am = 0;
-  float mx = n0;
-  if (n1 > mx) { mx = n1; am = 1; }
-  if (n2 > mx) { mx = n2; am = 2; }
+  float boot, diff;   // bootstrap value: the online net's max of Q(x'), or the target net's (trade_rule.h)
+  const int am = argmax3(qn[0], qn[1], qn[2], boot);
   const int slot = r.target_compat ? am : r.s_act[e];
   const float rew = r.s_rew[e];
-  // bootstrap value: max of Q(x') (online or target net); compat and Double DQN: the online argmax's value
-  float boot = mx;
   if (r.QT != nullptr) {
     const float* qt = r.QT + (size_t)e * 16;
+    // (target_value of trade_rule.h, written out: the call, which loads all three, costs this kernel 2 VGPRs less)
     if (r.target_compat || r.double_dqn) {
       boot = qt[am];
     } else {
       boot = fmaxf(fmaxf(qt[0], qt[1]), qt[2]);
     }
   }
-  const float rs = r.reward_scale != 1.f ? __fmul_rn(rew, r.reward_scale) : rew;
-  const float y = __fadd_rn(rs, __fmul_rn(r.gamma, boot));
+  const float y = td_target(rew, r.reward_scale, r.gamma, boot);
   const float qs = r.Q[(size_t)e * 16 + slot];
-  const float diff = __fsub_rn(qs, y);
-  float dq = r.coef * (r.td_clip > 0.f ? fminf(fmaxf(diff, -r.td_clip), r.td_clip) : diff);
-  if (r.output_relu && !(qs > 0.f)) dq = 0.f;
+  const float dq = td_dq(qs, y, r.coef, r.td_clip, r.output_relu, diff);
   float* d = r.DQ + (size_t)e * 16;
 #pragma unroll
   for (int j = 0; j < 16; ++j) d[j] = j == slot ? dq : 0.f;

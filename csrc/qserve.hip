@@ -24,6 +24,7 @@
 //  * otherwise (any stride): register gather with every load unconditional (clamped indices) and 7
 //    quads x 5 loads in flight per thread; activation tiles only in LDS (49 KB), two workgroups per CU.
 #include "common.h"
+#include "trade_rule.h"
 
 namespace st {
 namespace serve {
@@ -281,20 +282,12 @@ __global__ void __launch_bounds__(STREAM ? 512 : 256, STREAM ? 1 : 2) qserve_ker
           q[j] = acc[j] + b2[j];
           if (p.output_relu) q[j] = fmaxf(q[j], 0.f);
         }
-        int a = 0;
-        float best = q[0];
-        if (q[1] > best) { best = q[1]; a = 1; }
-        if (q[2] > best) { best = q[2]; a = 2; }
+        int a = argmax3(q[0], q[1], q[2]);
         if (p.steps != nullptr) {
-          uint32_t c0 = (uint32_t)row, c1 = (uint32_t)(p.seq & 0xFFFFFFFFull), c2 = (uint32_t)(p.seq >> 32),
-                   c3 = 2u;
-          philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-          const float u1 = u24(c0), u2 = u24(c1);
+          float u1, u2;
+          policy_draw((uint32_t)row, p.seq, p.key0, p.key1, u1, u2, 2u);   // (stream 2: the serving draw)
           const float st = STREAM ? sSteps[16 * wave + l16] : p.steps[row];
-          const bool exploit = u1 < fminf(p.eps, __fmul_rn(st, p.inv_ramp));
-          int rnd = (int)(u2 * 3.0f);
-          rnd = rnd > 2 ? 2 : rnd;
-          a = exploit ? a : rnd;
+          a = exploits(u1, p.eps, st, p.inv_ramp) ? a : random_action(u2);
         }
         p.actions[row] = a;
         if (p.q_out != nullptr) {

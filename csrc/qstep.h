@@ -1,7 +1,9 @@
 // Shared definitions of the fused online-DQN step kernels (qstep_fused.hip: 32-env chunks,
-// weights resident in LDS; qstep_wide.hip: 64-env chunks, layer-1 weights resident in VGPRs).
+// weights resident in LDS; qstep_wide.hip: 64-env chunks, layer-1 weights resident in VGPRs;
+// qstep_ws.hip: warp-specialised, with its target pass qtarget.hip and the ab/qstep_pipe.hip experiment).
 #pragma once
 #include "common.h"
+#include "trade_rule.h"
 
 namespace st {
 
@@ -102,12 +104,77 @@ ST_DEV float dpp_next_lane(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130, 0xF, 0xF, true));
 }
 
-ST_DEV float feat_price(float w, float inv, int mode) {
-  return mode ? __fsub_rn(__fmul_rn(w, inv), 1.0f) : w;
+// ----------------------------------------------------------------- the ws family's operand order
+// (qstep_ws.hip, qtarget.hip, ab/qstep_pipe.hip: a contract between these kernels and the weight-image maps)
+// input slot -> flat-layout column of W0^T.  Slots 0..191 are window columns; the last 16-wide k-step
+// is permuted so that the lanes holding an env's Q values (g4 == 0) also hold its tail features:
+//   g4 = 0: 201 budget, 202 shares, 203 constant 1 (layer-0 bias column), 200 (the window's last price)
+//   g4 = 1: 192..195;  g4 = 2: 196..199;  g4 = 3: pads 204..207
+ST_DEV int slot_col(int s) {
+  if (s < 192) return s;
+  const int t = s - 192, g = t >> 2, j = t & 3;
+  if (g == 0) return j < 3 ? 201 + j : 200;
+  if (g == 1) return 192 + j;
+  if (g == 2) return 196 + j;
+  return 204 + j;
 }
-ST_DEV float feat_budget(float b, float inv_b0, int mode) { return mode ? __fmul_rn(b, inv_b0) : b; }
-ST_DEV float feat_shares(int s, float last, float inv_b0, int mode) {
-  return mode ? __fmul_rn(__fmul_rn((float)s, last), inv_b0) : (float)s;
+// pi: position s (0..127, k-step s/32, lane group (s/8)%4, element s%8) of a B operand built in
+// registers from accumulator tiles 2*ks and 2*ks+1 -> hidden unit index
+ST_DEV int pi_unit(int s) {
+  const int ks = s >> 5, g = (s >> 3) & 3, j = s & 7;
+  return 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3);
+}
+
+ST_DEV s4v zero_s4() { s4v z = {0, 0, 0, 0}; return z; }
+ST_DEV s8v cat8(s4v a, s4v b) {
+  s8v r;
+  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
+  r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
+  return r;
+}
+ST_DEV s4v pk4(float a, float b, float c, float d) {
+  uint2 v;
+  v.x = pack_bf2(a, b);
+  v.y = pack_bf2(c, d);
+  return __builtin_bit_cast(s4v, v);
+}
+// relu then bf16 == bf16 then relu on the bits: a bf16 with the sign bit set is a negative int16, and
+// rounding never changes a sign (-0 -> +0 is fine); one v_pk_max_i16 per two values instead of a
+// NaN-canonicalising v_max_f32 pair per value
+typedef short s2v __attribute__((ext_vector_type(2)));
+ST_DEV s4v relu_bf(f4v v) {
+  const s2v z = {0, 0};
+  const s2v a = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[0], v[1])), z);
+  const s2v b = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[2], v[3])), z);
+  s4v r = {a[0], a[1], b[0], b[1]};
+  return r;
+}
+// accumulator tile -> bf16 masked by (act > 0), on packed integer ops: bf16(v) bits * min(act, 1)
+// (act >= 0 as a short: relu'd bf16 bits)
+// (inline asm: written in C, the compiler turns min(act, 1) * x back into a compare + select per value)
+ST_DEV unsigned mask2(unsigned x, unsigned act) {
+  unsigned m, r;
+  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(act), "v"(0x00010001u));
+  asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
+  return r;
+}
+ST_DEV s4v mask_pk(f4v v, s4v act) {
+  const uint2 a = __builtin_bit_cast(uint2, act);
+  uint2 r;
+  r.x = mask2(pack_bf2(v[0], v[1]), a.x);
+  r.y = mask2(pack_bf2(v[2], v[3]), a.y);
+  return __builtin_bit_cast(s4v, r);
+}
+// a wave-uniform acquire load of an LDS flag word
+ST_DEV int lds_acq(const int* w) {
+  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+// 16-byte loads from 4-byte-aligned addresses (the one padded bank copy is read at every shift): a memcpy
+// from a float pointer promises the compiler only 4-byte alignment; it is still one dwordx4 load
+ST_DEV float4 ldu4(const float* a) {
+  float4 v;
+  __builtin_memcpy(&v, a, sizeof(v));
+  return v;
 }
 
 }  // namespace st

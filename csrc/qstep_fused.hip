@@ -26,7 +26,7 @@
 //  * weight gradients stay in accumulator registers across all chunks of the
 //    workgroup (~190 VGPR/lane) and are written once per launch into a
 //    per-workgroup fp32 slab that optim.hip reduces (and RCCL all-reduces).
-#include "common.h"
+#include "qstep.h"
 
 namespace st {
 
@@ -34,43 +34,7 @@ constexpr int C = 32;       // envs per chunk
 constexpr int NT = 512;     // threads per workgroup: 8 waves = 2 per SIMD (latency hiding for the
                             // instruction-bound gather / env phases; see profiles/)
 constexpr int NW = NT / 64;
-constexpr int OUTP = 16;    // padded action dimension
 constexpr int SQ = OUTP + 8;
-constexpr int NSTAT = 8;
-
-// The launch parameters of this kernel: the leading fields of st::QStepParams (csrc/qstep.h) up to td_clip, in the
-// same order -- the host passes its one QStepParams mirror (sharetrade/ops/native.py) to st_qstep_launch, and this
-// kernel reads the prefix (pinned by tests/test_abi.py).  Its own name: one definition per struct in the library.
-struct FusedStepParams {
-  const float* prices;      // [E, T] env-major
-  const float* prices4;     // [4][E][T4] shifted replicas (series.hip: replicate4)
-  // env state + per-step outputs as ONE struct-of-arrays buffer [ENV_ROWS][E] of 4-byte
-  // words (rows below): one base pointer instead of nine keeps the kernel's scalar
-  // registers from spilling across the chunk loop
-  int* env;
-  const bf16_t* wq;         // bf16 flat params (kernel layout)
-  const float* wf;          // fp32 flat params (biases read from here)
-  float* slab;              // [G][P] per-workgroup partial gradients
-  float* stats;             // [G][NSTAT]
-  unsigned long long* ctrl;   // ctrl[0] = step index (read), ctrl[1] = step+1 (written by block 0)
-  int T, E, H, P, T4;
-  int off_w0, off_w1, off_b1, off_w2, off_b2;
-  float eps, inv_ramp, gamma, loss_coef, b0, inv_b0;
-  int s0, compat_env, target_compat, output_relu, feat_mode;
-  uint32_t key0, key1;
-  int env_offset;
-  unsigned long long* stamps;  // debug: s_memtime per phase of workgroup 0 ([iter][16]) or null
-  int slab_bf16, slab_rows;    // (64-env-chunk kernel fields, csrc/qstep.h: same layout)
-  unsigned* chunk_heads;
-  int reward_mode;             // 0: reward = change of portfolio value; 1: its one-step return
-  float td_clip;               // > 0: TD error clamped to [-td_clip, td_clip] (Huber loss)
-};
-
-// rows of FusedStepParams::env
-enum EnvRow : int { ER_POS = 0, ER_BUDGET, ER_SHARES, ER_VALUE, ER_RET_SUM, ER_EPISODES, ER_LAST_FINAL,
-                    ER_ACTION, ER_REWARD, ENV_ROWS };
-#define ENV_I(R, e) (p.env[(size_t)(R) * p.E + (e)])
-#define ENV_F(R, e) (reinterpret_cast<float*>(p.env)[(size_t)(R) * p.E + (e)])
 
 template <int INP, int H1P, int H2P>
 struct Geo {
@@ -105,35 +69,6 @@ struct Geo {
   static constexpr int NT0 = INP / 16 - 1;  // in-col tiles of dW0 (last tile is pure padding)
   static constexpr int NT1 = H1P / 16;
 };
-
-// A/B fragment from a row-major image: rows r0 + l16, k = k0 + 8*g4 .. +7
-ST_DEV s8v frag_row(const bf16_t* img, int S, int r0, int k0, int l16, int g4) {
-  return lds_ld8(img + (r0 + l16) * S + k0 + 8 * g4);
-}
-// Fragment with k running down the image rows (hardware transpose read):
-// element j of lane (g4, l16) = img[k0 + 8*g4 + j][c0 + l16]
-ST_DEV s8v frag_tr(const bf16_t* img, int S, int k0, int c0, int l16, int g4) {
-  const bf16_t* p = img + (k0 + 8 * g4 + (l16 >> 2)) * S + c0 + 4 * (l16 & 3);
-  s4v lo = lds_tr4(p);
-  s4v hi = lds_tr4(p + 4 * S);
-  s8v r;
-  r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
-  r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
-  return r;
-}
-
-// value of lane+1 (lane 63 gets 0): DPP wave_shl:1 — one VALU op instead of a ds_bpermute
-ST_DEV float dpp_next_lane(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x130, 0xF, 0xF, true));
-}
-
-ST_DEV float feat_price(float w, float inv, int mode) {
-  return mode ? __fsub_rn(__fmul_rn(w, inv), 1.0f) : w;
-}
-ST_DEV float feat_budget(float b, float inv_b0, int mode) { return mode ? __fmul_rn(b, inv_b0) : b; }
-ST_DEV float feat_shares(int s, float last, float inv_b0, int mode) {
-  return mode ? __fmul_rn(__fmul_rn((float)s, last), inv_b0) : (float)s;
-}
 
 // out^T[m][env] = sum_k A[m][k] * act[env][k]   (A = W^T image), MT m-tiles per wave x 2 env tiles.
 // Epilogue: + bias (fp32 LDS or none), ReLU, bf16 store into out image [env][m].
@@ -235,7 +170,7 @@ ST_DEV void bwd_data(const bf16_t* sWT, const bf16_t* sDZ, const bf16_t* sAct, b
 }
 
 template <int INP, int H1P, int H2P, int FEAT>
-__global__ void __launch_bounds__(NT, 2) qstep_fused_kernel(FusedStepParams p) {
+__global__ void __launch_bounds__(NT, 2) qstep_fused_kernel(QStepParams p) {
   using G = Geo<INP, H1P, H2P>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* sbf = reinterpret_cast<bf16_t*>(smem);
@@ -442,32 +377,18 @@ __global__ void __launch_bounds__(NT, 2) qstep_fused_kernel(FusedStepParams p) {
     if (wave == 0 && lane < C) {
       const int r = lane, e = ebase + r;
       const float q0 = sQ[r * 4 + 0], q1 = sQ[r * 4 + 1], q2 = sQ[r * 4 + 2];
-      int greedy = 0;
-      float best = q0;
-      if (q1 > best) { best = q1; greedy = 1; }
-      if (q2 > best) { best = q2; greedy = 2; }
+      const int greedy = argmax3(q0, q1, q2);
       const int ps = sEnvI[r * 4 + 0];
-      uint32_t c0 = (uint32_t)(p.env_offset + e), c1 = (uint32_t)(step & 0xFFFFFFFFull),
-               c2 = (uint32_t)(step >> 32), c3 = 0u;
-      philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-      const float u1 = u24(c0), u2 = u24(c1);
-      const bool exploit = u1 < fminf(p.eps, __fmul_rn((float)ps, p.inv_ramp));
-      int rnd = (int)(u2 * 3.0f);
-      rnd = rnd > 2 ? 2 : rnd;
-      const int a = exploit ? greedy : rnd;
+      float u1, u2;
+      policy_draw((uint32_t)(p.env_offset + e), step, p.key0, p.key1, u1, u2);
+      const bool exploit = exploits(u1, p.eps, (float)ps, p.inv_ramp);
+      const int a = exploit ? greedy : random_action(u2);
       const float b = sEnv[r * 8 + 0], vprev = sEnv[r * 8 + 1], vnew = sEnv[r * 8 + 2];
       const int s = sEnvI[r * 4 + 1];
-      const float bd = p.compat_env ? p.b0 : b;
-      const int sd = p.compat_env ? p.s0 : s;
-      const bool buy = (a == 0) && (bd >= vnew);
-      const bool sell = (a == 1) && (sd > 0);
-      const float b2 = buy ? __fsub_rn(bd, vnew) : (sell ? __fadd_rn(bd, vnew) : bd);
-      const int s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
-      const float cur = __fadd_rn(b, __fmul_rn((float)s, vprev));
-      const float nw = __fadd_rn(b2, __fmul_rn((float)s2, vnew));
-      float rew = __fsub_rn(nw, cur);
-      if (p.reward_mode) rew = cur > 0.f ? __fdiv_rn(rew, cur) : 0.f;
-        if (p.reward_mode == 2) rew = __fsub_rn(rew, __fmul_rn(__fmul_rn(rew, 0.5f), rew));   // growth: log1p to 2nd order
+      const Holding h2 = trade(a, trade_base(b, s, p.compat_env, p.b0, p.s0), vnew);
+      const float b2 = h2.budget;
+      const int s2 = h2.shares;
+      const float rew = reward(b, s, vprev, b2, s2, vnew, p.reward_mode);
       sEnv[r * 8 + 3] = b2;
       sEnv[r * 8 + 4] = rew;
       sEnvI[r * 4 + 1] = s2;
@@ -494,18 +415,14 @@ __global__ void __launch_bounds__(NT, 2) qstep_fused_kernel(FusedStepParams p) {
     if (wave == 0 && lane < C) {
       const int r = lane, e = ebase + r;
       const float n0 = sQN[r * 4 + 0], n1 = sQN[r * 4 + 1], n2 = sQN[r * 4 + 2];
-      int am = 0;
-      float mx = n0;
-      if (n1 > mx) { mx = n1; am = 1; }
-      if (n2 > mx) { mx = n2; am = 2; }
+      float mx, diff;
+      const int am = argmax3(n0, n1, n2, mx);
       const int a = sEnvI[r * 4 + 2];
       const float rew = sEnv[r * 8 + 4];
       const int slot = p.target_compat ? am : a;
-      const float y = __fadd_rn(rew, __fmul_rn(p.gamma, mx));
+      const float y = td_target(rew, 1.0f, p.gamma, mx);
       const float qs = sQ[r * 4 + slot];
-      const float diff = __fsub_rn(qs, y);
-      float dq = p.loss_coef * (p.td_clip > 0.f ? fminf(fmaxf(diff, -p.td_clip), p.td_clip) : diff);
-      if (p.output_relu && !(qs > 0.f)) dq = 0.f;
+      const float dq = td_dq(qs, y, p.loss_coef, p.td_clip, p.output_relu, diff);
       bf16_t* dqr = sDQ + r * SQ;
 #pragma unroll
       for (int j = 0; j < OUTP; ++j) dqr[j] = (j == slot) ? f2bf(dq) : (bf16_t)0;
@@ -622,7 +539,7 @@ __global__ void __launch_bounds__(NT, 2) qstep_fused_kernel(FusedStepParams p) {
 }
 
 template <int INP, int H1P, int H2P, int FEAT>
-static hipError_t launch_f(const FusedStepParams& p, int grid, hipStream_t stream) {
+static hipError_t launch_f(const QStepParams& p, int grid, hipStream_t stream) {
   using G = Geo<INP, H1P, H2P>;
   static bool attr = false;
   if (!attr) {
@@ -636,7 +553,7 @@ static hipError_t launch_f(const FusedStepParams& p, int grid, hipStream_t strea
 }
 
 template <int INP, int H1P, int H2P>
-static hipError_t launch_t(const FusedStepParams& p, int grid, hipStream_t stream) {
+static hipError_t launch_t(const QStepParams& p, int grid, hipStream_t stream) {
   return p.feat_mode ? launch_f<INP, H1P, H2P, 1>(p, grid, stream) : launch_f<INP, H1P, H2P, 0>(p, grid, stream);
 }
 
@@ -647,7 +564,7 @@ extern "C" int st_qstep_lds_bytes(int inp, int h1p, int h2p) {
   return -1;
 }
 
-extern "C" hipError_t st_qstep_launch(const st::FusedStepParams* p, int inp, int h1p, int h2p, int grid,
+extern "C" hipError_t st_qstep_launch(const st::QStepParams* p, int inp, int h1p, int h2p, int grid,
                                       hipStream_t stream) {
   if (inp == 224 && h1p == 128 && h2p == 128) return st::launch_t<224, 128, 128>(*p, grid, stream);
   return hipErrorInvalidValue;
@@ -655,7 +572,7 @@ extern "C" hipError_t st_qstep_launch(const st::FusedStepParams* p, int inp, int
 
 // struct sizes of this file's launch ABI, for the host mirrors' check (tests/test_abi.py; no HIP call)
 extern "C" int st_abi_qstep_fused(int* out, int n) {
-  const int sz[] = {(int)sizeof(st::FusedStepParams)};
+  const int sz[] = {(int)sizeof(st::QStepParams)};
   const int m = (int)(sizeof(sz) / sizeof(sz[0]));
   for (int i = 0; i < n && i < m; ++i) out[i] = sz[i];
   return m;

@@ -605,14 +605,10 @@ __global__ void __launch_bounds__(NT, 1) qstep_wide_kernel(QStepParams p) {
     auto a_w1 = [&](int i, int ks) { return wfrag_row(sW1, G::SW1, m0 + 16 * i, ks * 32, l16, g4); };
     if (DRAW_EARLY && wave == NW - 1) {
       const int pos = sEnvI[lane * 4 + 0];
-      uint32_t c0 = (uint32_t)(p.env_offset + ebase + lane), c1 = (uint32_t)(step & 0xFFFFFFFFull),
-               c2 = (uint32_t)(step >> 32), c3 = 0u;
-      philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-      const float u1 = u24(c0), u2 = u24(c1);
-      const bool exploit = u1 < fminf(p.eps, __fmul_rn((float)pos, p.inv_ramp));
-      int rnd = (int)(u2 * 3.0f);
-      rnd = rnd > 2 ? 2 : rnd;
-      sEnvI[lane * 4 + 2] = rnd | (exploit ? 8 : 0);   // exploit flag (bit 3) + random action
+      float u1, u2;
+      policy_draw((uint32_t)(p.env_offset + ebase + lane), step, p.key0, p.key1, u1, u2);
+      const bool exploit = exploits(u1, p.eps, (float)pos, p.inv_ramp);
+      sEnvI[lane * 4 + 2] = random_action(u2) | (exploit ? 8 : 0);   // exploit flag (bit 3) + random action
     }
     fwd_hidden<MT, INP, G::SX, G::SH1, false>(a_w0, sX, sH1, nullptr, m0, l16, g4);
     if (dyn && tid == 0) sCl[0] = dyn_chunk((unsigned)gx + claim_v);   // read in P9
@@ -649,10 +645,7 @@ __global__ void __launch_bounds__(NT, 1) qstep_wide_kernel(QStepParams p) {
         sQ[r * 4 + 0] = q[0];
         sQ[r * 4 + 1] = q[1];
         sQ[r * 4 + 2] = q[2];
-        int greedy = 0;
-        float best = q[0];
-        if (q[1] > best) { best = q[1]; greedy = 1; }
-        if (q[2] > best) { best = q[2]; greedy = 2; }
+        const int greedy = argmax3(q[0], q[1], q[2]);
         bool exploit;
         int rnd;
         if constexpr (DRAW_EARLY) {
@@ -661,28 +654,18 @@ __global__ void __launch_bounds__(NT, 1) qstep_wide_kernel(QStepParams p) {
           rnd = draw & 3;
         } else {
           const int ps = sEnvI[r * 4 + 0];
-          uint32_t c0 = (uint32_t)(p.env_offset + e), c1 = (uint32_t)(step & 0xFFFFFFFFull),
-                   c2 = (uint32_t)(step >> 32), c3 = 0u;
-          philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-          const float u1 = u24(c0), u2 = u24(c1);
-          exploit = u1 < fminf(p.eps, __fmul_rn((float)ps, p.inv_ramp));
-          rnd = (int)(u2 * 3.0f);
-          rnd = rnd > 2 ? 2 : rnd;
+          float u1, u2;
+          policy_draw((uint32_t)(p.env_offset + e), step, p.key0, p.key1, u1, u2);
+          exploit = exploits(u1, p.eps, (float)ps, p.inv_ramp);
+          rnd = random_action(u2);
         }
         const int a = exploit ? greedy : rnd;
         const float b = sEnv[r * ENVF + 0], vprev = sEnv[r * ENVF + 1], vnew = sEnv[r * ENVF + 2];
         const int s = sEnvI[r * 4 + 1];
-        const float bd = p.compat_env ? p.b0 : b;
-        const int sd = p.compat_env ? p.s0 : s;
-        const bool buy = (a == 0) && (bd >= vnew);
-        const bool sell = (a == 1) && (sd > 0);
-        const float b2 = buy ? __fsub_rn(bd, vnew) : (sell ? __fadd_rn(bd, vnew) : bd);
-        const int s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
-        const float cur = __fadd_rn(b, __fmul_rn((float)s, vprev));
-        const float nw = __fadd_rn(b2, __fmul_rn((float)s2, vnew));
-        float rew = __fsub_rn(nw, cur);
-        if (p.reward_mode) rew = cur > 0.f ? __fdiv_rn(rew, cur) : 0.f;
-        if (p.reward_mode == 2) rew = __fsub_rn(rew, __fmul_rn(__fmul_rn(rew, 0.5f), rew));   // growth: log1p to 2nd order
+        const Holding h2 = trade(a, trade_base(b, s, p.compat_env, p.b0, p.s0), vnew);
+        const float b2 = h2.budget;
+        const int s2 = h2.shares;
+        const float rew = reward(b, s, vprev, b2, s2, vnew, p.reward_mode);
         sEnv[r * ENVF + 3] = b2;
         sEnv[r * ENVF + 4] = rew;
         sEnvI[r * 4 + 1] = s2;
@@ -715,18 +698,14 @@ __global__ void __launch_bounds__(NT, 1) qstep_wide_kernel(QStepParams p) {
           n[j] = qn[j] + sB2[j];
           if (p.output_relu) n[j] = fmaxf(n[j], 0.f);
         }
-        int am = 0;
-        float mx = n[0];
-        if (n[1] > mx) { mx = n[1]; am = 1; }
-        if (n[2] > mx) { mx = n[2]; am = 2; }
+        float mx, diff;
+        const int am = argmax3(n[0], n[1], n[2], mx);
         const int araw = sEnvI[r * 4 + 2], a = araw & 3;
         const float rew = sEnv[r * ENVF + 4];
         const int slot = p.target_compat ? am : a;
-        const float y = __fadd_rn(rew, __fmul_rn(p.gamma, mx));
+        const float y = td_target(rew, 1.0f, p.gamma, mx);
         const float qs = sQ[r * 4 + slot];
-        const float diff = __fsub_rn(qs, y);
-        float dq = p.loss_coef * (p.td_clip > 0.f ? fminf(fmaxf(diff, -p.td_clip), p.td_clip) : diff);
-        if (p.output_relu && !(qs > 0.f)) dq = 0.f;
+        const float dq = td_dq(qs, y, p.loss_coef, p.td_clip, p.output_relu, diff);
         // dQ row: one nonzero at `slot`, written as two 16-byte stores
         // (slot < 3: only the first two words can be nonzero)
         const uint32_t dqb = (uint32_t)f2bf(dq);

@@ -127,24 +127,7 @@ static_assert(LDS_BYTES <= 163840, "LDS budget");
 static_assert(SLOT_BYTES % 16 == 0 && oSLOT % 16 == 0, "alignment");
 
 // ---------------------------------------------------------------------------------- index maps
-// input slot -> flat-layout column of W0^T.  Slots 0..191 are window columns; the last 16-wide k-step
-// is permuted so that the lanes holding an env's Q values (g4 == 0) also hold its tail features:
-//   g4 = 0: 201 budget, 202 shares, 203 constant 1 (layer-0 bias column), 200 (the window's last price)
-//   g4 = 1: 192..195;  g4 = 2: 196..199;  g4 = 3: pads 204..207
-ST_DEV int slot_col(int s) {
-  if (s < 192) return s;
-  const int t = s - 192, g = t >> 2, j = t & 3;
-  if (g == 0) return j < 3 ? 201 + j : 200;
-  if (g == 1) return 192 + j;
-  if (g == 2) return 196 + j;
-  return 204 + j;
-}
-// pi: position s (0..127, k-step s/32, lane group (s/8)%4, element s%8) of a B operand built in
-// registers from accumulator tiles 2*ks and 2*ks+1 -> hidden unit index
-ST_DEV int pi_unit(int s) {
-  const int ks = s >> 5, g = (s >> 3) & 3, j = s & 7;
-  return 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3);
-}
+// (slot_col / pi_unit: the input-slot and hidden-unit orders, csrc/qstep.h)
 // pi position of natural units 16 i + 4 q + (0..3) (4 consecutive positions)
 ST_DEV int pi_pos4(int i, int q) { return 32 * (i >> 1) + 8 * q + 4 * (i & 1); }
 // pi-ordered images (W1p, DZ2): 16-byte units of row R XOR-swizzled by 2 (R & 7) -- conflict-free 16-byte
@@ -157,49 +140,10 @@ ST_DEV int a_off(int r, int c) {
   return r * HP + ((((c >> 2) ^ ((4 * (r & 7)) | ((r >> 2) & 3)))) << 2) + (c & 3);
 }
 
-ST_DEV s4v zero_s4() { s4v z = {0, 0, 0, 0}; return z; }
 ST_DEV s8v zero_s8() { s8v z = {0, 0, 0, 0, 0, 0, 0, 0}; return z; }
-ST_DEV s8v cat8(s4v a, s4v b) {
-  s8v r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
-  r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-  return r;
-}
-ST_DEV s4v pk4(float a, float b, float c, float d) {
-  uint2 v;
-  v.x = pack_bf2(a, b);
-  v.y = pack_bf2(c, d);
-  return __builtin_bit_cast(s4v, v);
-}
-// relu then bf16 == bf16 then relu on the bits: a bf16 with the sign bit set is a negative int16, and
-// rounding never changes a sign (-0 -> +0 is fine); one v_pk_max_i16 per two values instead of a
-// NaN-canonicalising v_max_f32 pair per value
-typedef short s2v __attribute__((ext_vector_type(2)));
-ST_DEV s4v relu_bf(f4v v) {
-  const s2v z = {0, 0};
-  const s2v a = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[0], v[1])), z);
-  const s2v b = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[2], v[3])), z);
-  s4v r = {a[0], a[1], b[0], b[1]};
-  return r;
-}
 // accumulator tile -> bf16 masked by (act > 0) (act: bf16 bits, a positive value has a positive short)
 ST_DEV s4v mask_bf(f4v v, s4v act) {
   return pk4(act[0] > 0 ? v[0] : 0.f, act[1] > 0 ? v[1] : 0.f, act[2] > 0 ? v[2] : 0.f, act[3] > 0 ? v[3] : 0.f);
-}
-// same, on packed integer ops: bf16(v) bits * min(act, 1) (act >= 0 as a short: relu'd bf16 bits)
-// (inline asm: written in C, the compiler turns min(act, 1) * x back into a compare + select per value)
-ST_DEV unsigned mask2(unsigned x, unsigned act) {
-  unsigned m, r;
-  asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(act), "v"(0x00010001u));
-  asm("v_pk_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(x), "v"(m));
-  return r;
-}
-ST_DEV s4v mask_pk(f4v v, s4v act) {
-  const uint2 a = __builtin_bit_cast(uint2, act);
-  uint2 r;
-  r.x = mask2(pack_bf2(v[0], v[1]), a.x);
-  r.y = mask2(pack_bf2(v[2], v[3]), a.y);
-  return __builtin_bit_cast(s4v, r);
 }
 ST_DEV s4v lo4(s8v v) { s4v r = {v[0], v[1], v[2], v[3]}; return r; }
 ST_DEV s4v hi4(s8v v) { s4v r = {v[4], v[5], v[6], v[7]}; return r; }
@@ -255,9 +199,6 @@ constexpr int CTL_ABORT = 12;
 constexpr int CTL_NROUNDS = 13;
 ST_DEV int cid_word(int r) { const int s = r & 3; return s == 0 ? 0 : (s == 1 ? 9 : (s == 2 ? 14 : 15)); }
 constexpr int CID_SHIFT = 21, CID_MASK = (1 << CID_SHIFT) - 1;
-ST_DEV int lds_acq(const int* w) {
-  return __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
 ST_DEV void ws_fail(const QStepParams& p, int* ctl) {
   if ((threadIdx.x & 63) == 0) {
     __hip_atomic_store(ctl + CTL_ABORT, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -277,14 +218,6 @@ ST_DEV void ring_wait(const QStepParams& p, int* ctl, const int* w, Pred pred) {
     if (WS_SLEEP > 0) __builtin_amdgcn_s_sleep(WS_SLEEP);
     if (spin > SPIN_LIMIT) { ws_fail(p, ctl); break; }   // never expected: report, do not hang the GPU
   }
-}
-
-// 16-byte loads from 4-byte-aligned addresses (the one padded bank copy is read at every shift): a memcpy
-// from a float pointer promises the compiler only 4-byte alignment; it is still one dwordx4 load
-ST_DEV float4 ldu4(const float* a) {
-  float4 v;
-  __builtin_memcpy(&v, a, sizeof(v));
-  return v;
 }
 
 // env-state rows addressed as a uniform row base + a 32-bit byte offset, so the loads / stores use the
@@ -607,14 +540,8 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
       }
       // the epsilon-greedy draw (Philox, ~70 VALU with quarter-rate multiplies) depends only on (env, step):
       // issued here, the scheduler interleaves it with layer 1's MFMAs (VALU slots in the group pattern)
-      float u1, u2;
-      {
-        uint32_t c0 = (uint32_t)(p.env_offset + e), c1 = (uint32_t)(step & 0xFFFFFFFFull),
-                 c2 = (uint32_t)(step >> 32), c3 = 0u;
-        if (!WS_NOPHIL) philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-        u1 = u24(c0);
-        u2 = u24(c1);
-      }
+      float u1 = u24((uint32_t)(p.env_offset + e)), u2 = u24((uint32_t)step);   // (WS_NOPHIL: the raw counter)
+      if (!WS_NOPHIL) policy_draw((uint32_t)(p.env_offset + e), step, p.key0, p.key1, u1, u2);
       // ---------------------------------------------------------------- layer 1 of Q(x) and of Q(x')'s window
       f4v a1[8], a1n[8];
 #pragma unroll
@@ -714,25 +641,14 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
         q1 = qa[1] + b2v[1];
         q2 = qa[2] + b2v[2];
         if (p.output_relu) { q0 = fmaxf(q0, 0.f); q1 = fmaxf(q1, 0.f); q2 = fmaxf(q2, 0.f); }
-        int greedy = 0;
-        float best = q0;
-        if (q1 > best) { best = q1; greedy = 1; }
-        if (q2 > best) { best = q2; greedy = 2; }
-        const bool exploit = u1 < fminf(p.eps, __fmul_rn((KN && p.ramp_global) ? (float)step : (float)pos, p.inv_ramp));
-        int rnd = (int)(u2 * 3.0f);
-        rnd = rnd > 2 ? 2 : rnd;
+        const int greedy = argmax3(q0, q1, q2);
+        const bool exploit = exploits(u1, p.eps, (KN && p.ramp_global) ? (float)step : (float)pos, p.inv_ramp);
+        const int rnd = random_action(u2);
         act = exploit ? greedy : rnd;
-        const float bd = p.compat_env ? p.b0 : bud0;
-        const int sd = p.compat_env ? p.s0 : sh0;
-        const bool buy = (act == 0) && (bd >= vnew);
-        const bool sell = (act == 1) && (sd > 0);
-        b2 = buy ? __fsub_rn(bd, vnew) : (sell ? __fadd_rn(bd, vnew) : bd);
-        s2 = buy ? sd + 1 : (sell ? sd - 1 : sd);
-        const float cur = __fadd_rn(bud0, __fmul_rn((float)sh0, vprev));
-        const float nw = __fadd_rn(b2, __fmul_rn((float)s2, vnew));
-        rew = __fsub_rn(nw, cur);
-        if (p.reward_mode) rew = cur > 0.f ? __fdiv_rn(rew, cur) : 0.f;
-        if (p.reward_mode == 2) rew = __fsub_rn(rew, __fmul_rn(__fmul_rn(rew, 0.5f), rew));   // growth: log1p to 2nd order
+        const Holding h2 = trade(act, trade_base(bud0, sh0, p.compat_env, p.b0, p.s0), vnew);
+        b2 = h2.budget;
+        s2 = h2.shares;
+        rew = reward(bud0, sh0, vprev, b2, s2, vnew, p.reward_mode);
         Xn6 = pk4(feat_budget(b2, p.inv_b0, FEAT), feat_shares(s2, vnew, p.inv_b0, FEAT), 1.0f, fxn(vnew_w));
         st_explore += exploit ? 0.f : 1.f;
       }
@@ -786,21 +702,14 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
         if (KN && p.qt != nullptr) tq = *reinterpret_cast<const float4*>(p.qt + ((size_t)e * 3 + act) * 4);
         float n0 = qn[0] + b2v[0], n1 = qn[1] + b2v[1], n2 = qn[2] + b2v[2];
         if (p.output_relu) { n0 = fmaxf(n0, 0.f); n1 = fmaxf(n1, 0.f); n2 = fmaxf(n2, 0.f); }
-        int am = 0;
-        float mx = n0;
-        if (n1 > mx) { mx = n1; am = 1; }
-        if (n2 > mx) { mx = n2; am = 2; }
+        float vnext;   // the online net's max (QDecisionPolicyActor.scala:67-71)
+        const int am = argmax3(n0, n1, n2, vnext);
         slot = p.target_compat ? am : act;
-        float vnext = mx;   // the online net's max (QDecisionPolicyActor.scala:67-71)
-        if (KN && p.qt != nullptr)   // target value: of the online argmax (compat slot, double DQN) or its max
-          vnext = (p.target_compat || p.double_dqn) ? (am == 0 ? tq.x : (am == 1 ? tq.y : tq.z))
-                                                    : fmaxf(fmaxf(tq.x, tq.y), tq.z);
-        const float rsc = (KN && p.reward_scale != 1.0f) ? __fmul_rn(rew, p.reward_scale) : rew;
-        const float y = __fadd_rn(rsc, __fmul_rn(p.gamma, vnext));
+        if (KN && p.qt != nullptr) vnext = target_value(tq.x, tq.y, tq.z, am, p.target_compat || p.double_dqn);
+        const float y = td_target(rew, KN ? p.reward_scale : 1.0f, p.gamma, vnext);
         const float qs = slot == 0 ? q0 : (slot == 1 ? q1 : q2);
-        const float diff = __fsub_rn(qs, y);
-        dq = p.loss_coef * (p.td_clip > 0.f ? fminf(fmaxf(diff, -p.td_clip), p.td_clip) : diff);
-        if (p.output_relu && !(qs > 0.f)) dq = 0.f;
+        float diff;
+        dq = td_dq(qs, y, p.loss_coef, p.td_clip, p.output_relu, diff);
         float fdone = 0.f, ndone = 0.f;
         if (pos + 1 >= p.T - HWIN) {
           fdone = __fadd_rn(b2, __fmul_rn((float)s2, vnew));

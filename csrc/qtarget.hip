@@ -34,43 +34,10 @@ constexpr int oW2 = oW1 + HP * HP * 2;         // W2 [4][128] bf16, columns in p
 constexpr int oB1 = oW2 + 4 * HP * 2;          // b1 [128] f32
 constexpr int LDS_BYTES = oB1 + HP * 4;
 
-ST_DEV int slot_col(int s) {
-  if (s < 192) return s;
-  const int t = s - 192, g = t >> 2, j = t & 3;
-  if (g == 0) return j < 3 ? 201 + j : 200;
-  if (g == 1) return 192 + j;
-  if (g == 2) return 196 + j;
-  return 204 + j;
-}
-// position s of a B operand built from accumulator tiles 2 ks, 2 ks + 1 -> hidden unit (qstep_ws.hip's pi)
-ST_DEV int pi_unit(int s) {
-  const int ks = s >> 5, g = (s >> 3) & 3, j = s & 7;
-  return 32 * ks + 16 * (j >> 2) + 4 * g + (j & 3);
-}
 // W1 image: 16-byte chunk c / 8 of row r stored at chunk (c / 8) ^ (r & 15).  The fragment read of unit tile
 // i, k-step ks (lane (l16, g4): row 16 i + l16, chunk 4 ks + g4) then hits 16 different chunks per lane group
 // instead of one bank group 16 times (256-byte rows)
 ST_DEV int w1_off(int r, int c) { return r * HP + ((((c >> 3) ^ (r & 15))) << 3) + (c & 7); }
-ST_DEV s8v cat8(s4v a, s4v b) {
-  s8v r;
-  r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3];
-  r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-  return r;
-}
-ST_DEV s4v pk4(float a, float b, float c, float d) {
-  uint2 v;
-  v.x = pack_bf2(a, b);
-  v.y = pack_bf2(c, d);
-  return __builtin_bit_cast(s4v, v);
-}
-typedef short s2v __attribute__((ext_vector_type(2)));
-ST_DEV s4v relu_bf(f4v v) {
-  const s2v z = {0, 0};
-  const s2v a = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[0], v[1])), z);
-  const s2v b = __builtin_elementwise_max(__builtin_bit_cast(s2v, pack_bf2(v[2], v[3])), z);
-  s4v r = {a[0], a[1], b[0], b[1]};
-  return r;
-}
 // a 16-wide k-step as a 16x16x32 MFMA with the upper halves of both operands zero (same cost on gfx950).  Not
 // v_mfma_f32_16x16x16_bf16: reading a 16x16x32 result as its accumulator needs >= 4 wait states on MI355X
 // (tools/ubench/mfma_raw_gen.py), hipcc (ROCm 7.2) emitted that pair with 1 here and the 16x16x16 MFMA saw the
@@ -80,12 +47,6 @@ ST_DEV f4v mfma32z(s4v a, s4v b, f4v c) {
   const s4v z = {0, 0, 0, 0};
   return mfma32(cat8(a, z), cat8(b, z), c);
 }
-ST_DEV float4 ldu4(const float* a) {
-  float4 v;
-  __builtin_memcpy(&v, a, sizeof(v));
-  return v;
-}
-
 struct QTargetParams {
   const float* prices4;   // one padded copy of the bank [E][T4]
   const int* env;         // env state rows (qstep.h EnvRow)
@@ -157,8 +118,8 @@ __global__ void __launch_bounds__(64 * NWV, 1) qtarget_kernel(QTargetParams p) {
     asm volatile("" : "+s"(zo));
     const bf16_t* W0i = W0 + zo;
     // ---------------------------------------------------------------- x' features of the wave's TPW env tiles
-    float vnew[TPW], invn[TPW], bd[TPW], vnw[TPW];   // vnw: vnew in the window's units (U16: the tick)
-    int sd[TPW];
+    float vnew[TPW], invn[TPW], vnw[TPW];   // vnw: vnew in the window's units (U16: the tick)
+    Holding hd[TPW];
     s8v X[TPW][6];
     s4v Xw[TPW];
 #pragma unroll
@@ -221,9 +182,8 @@ __global__ void __launch_bounds__(64 * NWV, 1) qtarget_kernel(QTargetParams p) {
         Xw[q] = pk4(fxn(u.x), fxn(u.y), fxn(u.z), fxn(u.w));
       }
       }
-      // the three candidates: Buy, Sell, Hold from (bd, sd) -- the env's own transition
-      bd[q] = p.compat_env ? p.b0 : bud;
-      sd[q] = p.compat_env ? p.s0 : sh;
+      // the three candidates: Buy, Sell, Hold from hd -- the env's own transition
+      hd[q] = trade_base(bud, sh, p.compat_env, p.b0, p.s0);
     }
     // ---------------------------------------------------------------- layer 1 over the window (shared by the
     // candidates): one W0 fragment read per (unit tile, k-step) feeds the TPW env tiles' MFMAs
@@ -251,12 +211,10 @@ __global__ void __launch_bounds__(64 * NWV, 1) qtarget_kernel(QTargetParams p) {
       s8v H1[TPW][4];
 #pragma unroll
       for (int q = 0; q < TPW; ++q) {
-        const bool buy = a == 0 && bd[q] >= vnew[q], sell = a == 1 && sd[q] > 0;
-        const float b2 = buy ? __fsub_rn(bd[q], vnew[q]) : (sell ? __fadd_rn(bd[q], vnew[q]) : bd[q]);
-        const int s2 = buy ? sd[q] + 1 : (sell ? sd[q] - 1 : sd[q]);
+        const Holding h2 = trade(a, hd[q], vnew[q]);
         const float fvn = FEAT ? __fmaf_rn(vnw[q], invn[q], -1.0f) : vnew[q];
-        const s4v tl = g4 == 0 ? pk4(feat_budget(b2, p.inv_b0, FEAT), feat_shares(s2, vnew[q], p.inv_b0, FEAT),
-                                     1.0f, fvn)
+        const s4v tl = g4 == 0 ? pk4(feat_budget(h2.budget, p.inv_b0, FEAT),
+                                     feat_shares(h2.shares, vnew[q], p.inv_b0, FEAT), 1.0f, fvn)
                                : s4v{0, 0, 0, 0};
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {

@@ -81,7 +81,10 @@ class OptimParams(C.Structure):
     ]
 
 
-# rows of QStepParams::env (csrc/qstep_fused.hip EnvRow): int32 / fp32 words
+# agent.reward_mode -> the kernels' code (reward() of csrc/trade_rule.h)
+REWARD_MODES = {"absolute": 0, "relative": 1, "growth": 2}
+
+# rows of QStepParams::env (csrc/qstep.h EnvRow): int32 / fp32 words
 ENV_ROWS = ("pos", "budget", "shares", "value", "ret_sum", "episodes", "last_final", "actions_out", "rewards_out")
 
 

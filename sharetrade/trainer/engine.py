@@ -422,7 +422,7 @@ class VectorEngine:
         q.key0, q.key1 = int(self.key0), int(self.key1)
         q.env_offset = self.env_offset
         q.chunk_heads = native.ptr(self.chunk_heads) if self.chunk_heads is not None else None
-        q.reward_mode = {"absolute": 0, "relative": 1, "growth": 2}[cfg.agent.reward_mode]
+        q.reward_mode = native.REWARD_MODES[cfg.agent.reward_mode]
         q.td_clip = float(cfg.agent.td_clip)
         self.kernel_err = torch.zeros(4, dtype=torch.int32, device=self.device)
         q.err = native.ptr(self.kernel_err)

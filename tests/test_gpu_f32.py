@@ -134,6 +134,35 @@ def test_fp32_engine_matches_torch_engine(dev, preset):
         assert _rel(g.params.cpu(), c.params) < 1e-5
 
 
+@pytest.mark.parametrize("path", ["f32_rows", "f32_batched"])
+def test_fp32_reward_modes_and_td_clip_match_oracle(dev, path):
+    """agent.reward_mode = absolute / relative / growth and agent.td_clip (Huber) on the fp32 row kernels (8 envs)
+    and the batched fp32 step (64 envs, forced on) vs the torch oracle with the kernel's actions: identical rewards
+    and transitions, the gradient within fp32 summation-order tolerance."""
+    from test_oracle import RULE_CASES, RULE_STEP, rule_cfg, rule_coverage, rule_oracle, rule_prices, rule_state
+
+    from sharetrade.trainer.engine import VectorEngine
+
+    for mode, clip in RULE_CASES:
+        cfg, E = rule_cfg(path, mode, clip)
+        prices = rule_prices(E)
+        eng = VectorEngine(cfg, prices=prices, device=dev, envs=E)
+        assert eng.kernel == "fp32_rows" and eng.f32_path == ("batched" if path == "f32_batched" else "rows")
+        st0 = rule_state(eng, prices)
+        eng.ctrl.fill_(RULE_STEP)
+        params = eng.params.detach().cpu().clone()
+        grad = eng.native_grad().detach().cpu().clone()
+        torch.cuda.synchronize()
+        acts, rew = eng.actions_out.cpu().clone(), eng.rewards_out.cpu().clone()
+        rule_coverage(acts, st0)
+        ns, g_ref, info = rule_oracle(cfg, eng, prices, st0, params, forced_actions=acts)
+        assert torch.equal(info["reward"], rew), (mode, clip)
+        for k in ("budget", "shares", "value", "pos"):
+            assert torch.equal(getattr(ns, k), getattr(eng.state, k).cpu()), (mode, clip, k)
+        print(f"[meas] {path} reward_mode={mode} td_clip={clip} grad_rel={_rel(grad, g_ref):.3e}")
+        assert _rel(grad, g_ref) < 1e-5, (mode, clip, _rel(grad, g_ref))
+
+
 def test_fp32_engine_compat_reproduces_reference_portfolio(dev):
     """Quirk Q1 on the GPU fp32 path: reward 0 at every step, final portfolio = budget."""
     from sharetrade.config import preset_config

@@ -306,15 +306,17 @@ def test_dynamic_chunk_schedule_matches_static(native_built):
 
 @pytest.mark.parametrize("chunk", [32, 64])
 def test_reward_modes_and_td_clip_match_oracle(native_built, chunk):
-    """agent.reward_mode = relative / absolute and agent.td_clip (Huber) in both step kernels vs the
+    """agent.reward_mode = absolute / relative / growth and agent.td_clip (Huber) in both step kernels vs the
     torch oracle: identical rewards and transitions, gradients within the bf16 tolerance."""
+    from test_oracle import RULE_CASES, rule_coverage
+
     from sharetrade.env import trading as tr
     from sharetrade.trainer.engine import VectorEngine
 
     E = 128
     prices = _prices(E)
     dev = torch.device("cuda", 0)
-    for mode, clip in (("absolute", 0.0), ("relative", 0.0), ("absolute", 0.5)):
+    for mode, clip in RULE_CASES:
         cfg = _cfg(False)
         cfg.agent.epsilon = 0.5
         cfg.agent.reward_mode, cfg.agent.td_clip = mode, clip
@@ -336,8 +338,9 @@ def test_reward_modes_and_td_clip_match_oracle(native_built, chunk):
             target_slot=cfg.agent.target_slot, gamma=cfg.agent.gamma, output_relu=cfg.model.output_relu,
             epsilon=cfg.agent.epsilon, ramp=cfg.agent.ramp, seed=cfg.agent.seed, rank=0, step=5,
             loss_coef=eng.loss_coef, reward_mode=mode, td_clip=clip, emulate_bf16=True, forced_actions=acts)
+        rule_coverage(acts, st0)
         assert torch.equal(info["reward"], rew), mode
-        if mode == "relative":
+        if mode != "absolute":
             assert float(rew.abs().max()) < 0.5   # one-step returns, not dollars
         for k in ("budget", "shares", "value", "pos"):
             assert torch.equal(getattr(ns, k), getattr(eng.state, k).cpu()), (mode, k)

@@ -148,6 +148,41 @@ def test_ws_episode_end_and_reset(native_built, kernel):
     assert torch.equal(ns.last_final[done], eng.state.last_final.cpu()[done])
 
 
+def test_ws_reward_modes_and_td_clip_match_oracle(native_built):
+    """agent.reward_mode = absolute / relative / growth and agent.td_clip (Huber) on the ws kernel vs the torch
+    oracle: identical rewards and transitions, gradients within test_ws_matches_oracle's bounds.  E = 128 on one
+    workgroup: two 64-env chunks, two tiles per data wave, and the 4-slot ring wraps."""
+    from test_oracle import RULE_CASES, RULE_STEP, rule_cfg, rule_coverage, rule_prices, rule_state
+
+    from sharetrade.trainer.engine import VectorEngine
+
+    dev = torch.device("cuda", 0)
+    for mode, clip in RULE_CASES:
+        cfg, E = rule_cfg("ws", mode, clip)
+        prices = rule_prices(E, tick16=True)
+        eng = VectorEngine(cfg, prices=prices, device=dev, envs=E)
+        assert eng.step_kernel == "ws" and E == 128
+        st0 = rule_state(eng, prices)
+        eng.ctrl.fill_(RULE_STEP)
+        params = eng.params.detach().cpu().clone()
+        grad = eng.native_grad().detach().cpu().clone()
+        torch.cuda.synchronize()
+        assert int(eng.kernel_err.sum()) == 0, "ring wait gave up"
+        acts, rew = eng.actions_out.cpu().clone(), eng.rewards_out.cpu().clone()
+        rule_coverage(acts, st0)
+        ns, g_ref, info = _oracle(cfg, prices, st0, params, eng.layout, RULE_STEP, eng.loss_coef, emulate_bf16=True,
+                                  forced_actions=acts)
+        assert torch.equal(info["reward"], rew), (mode, clip)
+        for k in ("budget", "shares", "value", "pos"):
+            assert torch.equal(getattr(ns, k), getattr(eng.state, k).cpu()), (mode, clip, k)
+        L = eng.layout
+        for l in range(L.n_layers):
+            print(f"[meas] ws reward_mode={mode} td_clip={clip} layer={l} w_rel_bf16={_rel(L.w(grad, l), L.w(g_ref, l)):.3e}")
+            assert _rel(L.w(grad, l), L.w(g_ref, l)) < 5e-3, (mode, clip, l)
+            if l > 0:
+                assert _rel(L.b(grad, l), L.b(g_ref, l)) < 5e-3, (mode, clip, l)
+
+
 def test_ws_and_wide_agree_over_steps(native_built):
     """Ten captured steps of each kernel from the same start: the learned parameters stay close (both are
     bf16 MFMA steps of the same math; fp32 summation orders differ) and the env statistics agree."""

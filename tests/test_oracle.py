@@ -81,6 +81,101 @@ def test_env_transition_rules():
     assert r.tolist() == pytest.approx([0.0, 4.0, 0.0, 1.0])
 
 
+def test_env_transition_growth_reward():
+    """growth = r - (r * 0.5) * r of the relative reward, in fp32 with those three roundings; relative and growth
+    are 0 where the previous portfolio value is not positive."""
+    g = torch.Generator().manual_seed(7)
+    n = 64
+    b = torch.rand(n, generator=g) * 200.0
+    s = torch.randint(0, 3, (n,), generator=g, dtype=torch.int32)
+    a = torch.randint(0, 3, (n,), generator=g, dtype=torch.int32)
+    v_prev = 40.0 + 20.0 * torch.rand(n, generator=g)
+    v_new = v_prev * (1.0 + 0.05 * (torch.rand(n, generator=g) - 0.5))
+    b[:4], s[:4] = 0.0, 0            # previous value b + s * v_prev = 0 ...
+    b[4:8], v_prev[4:8] = -5.0, 0.0  # ... and negative
+    kw = dict(compat=False, b0=2400.0, s0=0)
+    b2r, s2r, rel = tr.env_transition(a, b, s, v_prev, v_new, relative=True, **kw)
+    b2g, s2g, gro = tr.env_transition(a, b, s, v_prev, v_new, relative=True, growth=True, **kw)
+    assert torch.equal(b2r, b2g) and torch.equal(s2r, s2g)
+    assert rel.dtype == torch.float32 and gro.dtype == torch.float32
+    assert torch.equal(gro, rel - (rel * 0.5) * rel)
+    assert torch.equal(gro, tr.env_transition(a, b, s, v_prev, v_new, growth=True, **kw)[2])   # growth implies relative
+    assert float(rel[8:].abs().max()) > 0
+    assert not torch.equal(gro[8:], rel[8:])
+    assert torch.all(rel[:8] == 0) and torch.all(gro[:8] == 0)
+
+
+# The reward-mode / TD-clip cases under which every GPU step path is pinned to engine_step_ref
+# (test_gpu_qstep.py, test_gpu_qstep_ws.py, test_gpu_f32.py), and the env state they start from
+RULE_CASES = (("absolute", 0.0), ("relative", 0.0), ("absolute", 0.5), ("growth", 0.0), ("growth", 0.5))
+RULE_STEP = 5
+
+
+def rule_prices(E, tick16=False):
+    from sharetrade.data.prices import random_walk, tick16_quantize
+
+    p = random_walk(400, 50.0, 0.02, 3, n_series=E).astype(np.float32)
+    return torch.from_numpy(tick16_quantize(p) if tick16 else p)
+
+
+def rule_cfg(path, mode, clip):
+    """path: "wide" (E = 128, 32- / 64-env chunks), "ws" (E = 128, one workgroup), "f32_rows" (E = 8),
+    "f32_batched" (E = 64) -> (cfg, E)."""
+    cfg = preset_config("flagship" if path in ("wide", "ws") else "intended")
+    cfg.agent.epsilon = 0.5
+    cfg.agent.reward_mode, cfg.agent.td_clip = mode, clip
+    if path == "ws":
+        cfg.engine.step_kernel, cfg.engine.grid = "ws", 1
+    elif path != "wide":
+        cfg.engine.dtype = "fp32"
+        cfg.agent.ramp = 4.0   # (as test_gpu_f32.py: with 8 envs at positions < 24 the default ramp never exploits)
+        cfg.engine.f32_batched = "on" if path == "f32_batched" else "off"
+    return cfg, {"wide": 128, "ws": 128, "f32_rows": 8, "f32_batched": 64}[path]
+
+
+def rule_state(eng, prices):
+    """Positions spread over 3 e % 150, shares e % 3, value from the bank, step counter RULE_STEP."""
+    dev = eng.state.pos.device
+    e = torch.arange(prices.shape[0], dtype=torch.int32, device=dev)
+    eng.state.pos.copy_(e * 3 % 150)
+    eng.state.shares.copy_(e % 3)
+    eng.state.value.copy_(prices[:, 0].to(dev))
+    return eng.state.clone().to("cpu")
+
+
+def rule_oracle(cfg, eng, prices, st0, params, forced_actions=None):
+    return tr.engine_step_ref(
+        prices, st0, params, eng.layout, history=cfg.model.history, feature_mode=cfg.env.features,
+        budget0=cfg.env.budget, shares0=cfg.env.shares, compat_env=cfg.env.compat_decisions,
+        target_slot=cfg.agent.target_slot, gamma=cfg.agent.gamma, output_relu=cfg.model.output_relu,
+        epsilon=cfg.agent.epsilon, ramp=cfg.agent.ramp, seed=cfg.agent.seed, rank=0, step=RULE_STEP,
+        loss_coef=eng.loss_coef, reward_mode=cfg.agent.reward_mode, td_clip=cfg.agent.td_clip,
+        emulate_bf16=(cfg.engine.dtype == "bf16"), forced_actions=forced_actions)
+
+
+def rule_coverage(actions, st0):
+    """Every action occurs, and at least one Sell is refused (no share to sell)."""
+    actions = actions.cpu()
+    assert sorted(set(actions.tolist())) == [0, 1, 2], actions.tolist()
+    assert bool(((actions == 1) & (st0.shares == 0)).any()), "no refused Sell"
+
+
+@pytest.mark.parametrize("path", ["wide", "ws", "f32_rows", "f32_batched"])
+def test_rule_cases_cover_every_action(path):
+    """The set-ups of the GPU reward-mode tests, with the oracle alone: under each case Buy, Sell and Hold are all
+    taken and a Sell is refused, so the kernels' transition is compared on every branch."""
+    from sharetrade.trainer.engine import VectorEngine
+
+    for mode, clip in RULE_CASES:
+        cfg, E = rule_cfg(path, mode, clip)
+        prices = rule_prices(E, tick16=(path == "ws"))
+        eng = VectorEngine(cfg, prices=prices, device=torch.device("cpu"), envs=E, backend="torch")
+        st0 = rule_state(eng, prices)
+        _, _, info = rule_oracle(cfg, eng, prices, st0, eng.params.detach().clone())
+        rule_coverage(info["actions"], st0)
+        assert bool(info["exploit"].any()) and not bool(info["exploit"].all())
+
+
 def test_compat_msft_run_reproduces_reference_portfolio():
     """Reference quirk Q1: every worker ends at exactly its initial budget."""
     from sharetrade.trainer.engine import VectorEngine
