@@ -1,0 +1,383 @@
+// Backtest of a frozen policy on CDNA4 (gfx950): whole episodes of the Buy/Sell/Hold env in one launch.
+//
+// For env e and day t = start .. start + steps - 1 the rule is the engine's (csrc/trade_rule.h, oracle
+// sharetrade/serve/rollout.py::reference_rollout): window prices[e, t : t+H] -> features -> the flagship
+// 2x128 bf16 Q-net (224 -> 128 -> 128 -> 16, the forward of csrc/qserve.hip) -> argmax -> epsilon-greedy
+// (Philox stream 4, exploit ramp on the day t) -> trade at v = prices[e, t+H].  Only the budget and the
+// shares of the 203 inputs depend on earlier actions, and consecutive windows share H - 1 prices, so a
+// workgroup owns its envs for the whole launch:
+//  * every weight lives in VGPRs (a wave owns 32 hidden units of both hidden layers plus the output
+//    fragments: 104 registers per lane), loaded once per workgroup;
+//  * the env state (budget, shares, trade counts) lives in the registers of the lane that ends up with
+//    the env's Q row (waves 0 .. NET-1, lanes 0 .. 15);
+//  * prices sit in LDS in a ring of 256 values per env: the first block loads H + D of them, every later
+//    block of D days loads the D new ones (prefetched into registers a block ahead), so each price is read
+//    from HBM once; 1 / last of a block's D windows is computed once per block;
+//  * per day: features of the 32 envs (one row per wave pass, lanes along the columns) -> layer 1 ->
+//    layer 2 -> output + trade, four LDS-only barriers, no global load on the chain.
+// 32 envs per workgroup keep the LDS at 61 KB: two workgroups (four independent 16-env tiles) per CU, one
+// workgroup's serial chain under the other's MFMA phases.
+#include <type_traits>
+
+#include "common.h"
+#include "trade_rule.h"
+
+namespace st {
+namespace rollout {
+
+constexpr int INP = 224, HP = 128;              // padded dims of the flagship layout (models/qnet.py)
+constexpr int C = 32;                           // envs per workgroup
+constexpr int NW = 4, NT = 64 * NW;
+constexpr int NET = C / 16;                     // 16-env tiles per workgroup
+constexpr int MT = HP / (16 * NW);              // 16-unit m-tiles per wave
+constexpr int KS0 = INP / 32, KS1 = HP / 32;
+constexpr int SX = INP + 16, SH = HP + 16;      // activation row strides (bf16)
+constexpr int D = 32;                           // days per price block
+constexpr int RING = 256, SP = RING + 1;        // price ring per env (floats), padded row stride
+constexpr int RPW = C / NW;                     // feature rows per wave
+static_assert(INP - 3 + D <= RING, "a block's windows and trade prices must fit the ring");
+static_assert(C * D == 4 * NT && NT / D == 8, "block loader: 4 values per thread, 8 rows per pass");
+
+constexpr int OFF_X = 0;                            // bf16 [C][SX]; H2 [C][SH] over it
+constexpr int OFF_H1 = OFF_X + C * SX * 2;          // bf16 [C][SH]
+constexpr int OFF_P = OFF_H1 + C * SH * 2;          // fp32 [C][SP] price ring: price j at column j % RING
+constexpr int OFF_INV = OFF_P + C * SP * 4;         // fp32 [C][D] 1 / last price of the block's windows
+constexpr int OFF_FB = OFF_INV + C * D * 4;         // fp32 [C] budget feature of the coming day
+constexpr int OFF_FS = OFF_FB + C * 4;              // fp32 [C] shares feature of the coming day
+constexpr int LDS_BYTES = OFF_FS + C * 4;
+static_assert(OFF_H1 % 16 == 0 && OFF_P % 16 == 0 && OFF_INV % 16 == 0 && OFF_FB % 16 == 0, "16-byte carves");
+
+// s_waitcnt lgkmcnt(0) only: the barriers order LDS traffic and leave the trace stores and the price
+// prefetch in flight (a __syncthreads() drains them: vmcnt(0))
+ST_DEV void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4)); }
+ST_DEV void bar() {
+  wait_lgkm0();
+  asm volatile("s_barrier" ::: "memory");
+}
+
+struct RolloutParams {
+  const float* prices;     // [E][ld] fp32, T valid values per row
+  const bf16_t* wq;        // bf16 flat params (engine layout)
+  const float* wf;         // fp32 flat params (biases)
+  const float* budget;     // [E] initial budget, or null = b0
+  const int* shares;       // [E] initial shares, or null = s0
+  float* out_budget;       // [E]
+  int* out_shares;         // [E]
+  float* out_portfolio;    // [E] budget + shares * last trade price
+  int* out_buys;           // [E] executed buys
+  int* out_sells;          // [E] executed sells
+  signed char* tr_actions; // [E][steps] or null
+  float* tr_q;             // [E][steps][3] or null
+  float* tr_equity;        // [E][steps] or null: the portfolio after each day's trade
+  int E, ld, T, H, start, steps;
+  int off_w0, off_w1, off_b1, off_w2, off_b2;
+  int feat_mode, output_relu, compat_env;
+  int s0;
+  float b0, inv_b0, eps, inv_ramp;   // eps = inf: greedy
+  uint32_t key0, key1, env_offset;   // draw counter: (env_offset + e, day, 0, stream 4)
+};
+
+__global__ void __launch_bounds__(NT, 2) qrollout_kernel(RolloutParams p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* sX = reinterpret_cast<bf16_t*>(smem + OFF_X);
+  bf16_t* sH1 = reinterpret_cast<bf16_t*>(smem + OFF_H1);
+  bf16_t* sH2 = sX;
+  float* sP = reinterpret_cast<float*>(smem + OFF_P);
+  float* sInv = reinterpret_cast<float*>(smem + OFF_INV);
+  float* sFB = reinterpret_cast<float*>(smem + OFF_FB);
+  float* sFS = reinterpret_cast<float*>(smem + OFF_FS);
+  const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int m0 = 16 * MT * wave;
+  const int H = p.H, mode = p.feat_mode;
+  const bool greedy = __builtin_isinf(p.eps);
+
+  // ---------------------------------------------------------------- weights -> VGPRs (once)
+  s8v aW0[MT][KS0], aW1[MT][KS1], aW2[KS1];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    const bf16_t* w0 = p.wq + p.off_w0 + (size_t)(m0 + 16 * i + l16) * INP + 8 * g4;
+#pragma unroll
+    for (int ks = 0; ks < KS0; ++ks) aW0[i][ks] = *reinterpret_cast<const s8v*>(w0 + ks * 32);
+    const bf16_t* w1 = p.wq + p.off_w1 + (size_t)(m0 + 16 * i + l16) * HP + 8 * g4;
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) aW1[i][ks] = *reinterpret_cast<const s8v*>(w1 + ks * 32);
+  }
+  {
+    const bf16_t* w2 = p.wq + p.off_w2 + (size_t)l16 * HP + 8 * g4;
+#pragma unroll
+    for (int ks = 0; ks < KS1; ++ks) aW2[ks] = *reinterpret_cast<const s8v*>(w2 + ks * 32);
+  }
+  float bb[MT][4];
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bb[i][j] = p.wf[p.off_b1 + m0 + 16 * i + 4 * g4 + j];
+  float b2[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) b2[j] = p.wf[p.off_b2 + j];
+
+  const int tend = p.start + p.steps;
+  const int ntiles = (p.E + C - 1) / C;
+  // block loader: thread = (column tid % D of the block, rows tid / D + 8 k); rows past E re-read row E - 1
+  const int lc = tid & (D - 1), lr = tid / D;
+
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int r0 = tile * C;
+    // the env of this lane: waves 0 .. NET-1, lanes 0 .. 15 (where the output MFMA leaves q[0..2])
+    const bool owner = wave < NET && g4 == 0;
+    const int myrow = owner ? 16 * wave + l16 : 0;
+    const int env = r0 + myrow;
+    const bool live = owner && env < p.E;
+    float b = p.b0, vlast = 0.f;
+    int s = p.s0, nbuy = 0, nsell = 0;
+    if (owner) {
+      const int ec = min(env, p.E - 1);
+      if (p.budget != nullptr) b = p.budget[ec];
+      if (p.shares != nullptr) s = p.shares[ec];
+    }
+    // ------------------------------------------------------------ first block: prices start .. start+H+D-1
+#pragma unroll 1
+    for (int i = 0; i < RPW; ++i) {
+      const int r = wave * RPW + i;
+      const float* row = p.prices + (size_t)min(r0 + r, p.E - 1) * (size_t)p.ld;
+      for (int c = lane; c < H + D; c += 64) {
+        const int j = p.start + c;
+        sP[r * SP + (j & (RING - 1))] = row[min(j, p.T - 1)];
+      }
+    }
+    bar();
+    if (owner) {
+      const float last = sP[myrow * SP + ((p.start + H - 1) & (RING - 1))];
+      sFB[myrow] = feat_budget(b, p.inv_b0, mode);
+      sFS[myrow] = feat_shares(s, last, p.inv_b0, mode);
+    }
+
+#pragma unroll 1
+    for (int t0 = p.start; t0 < tend; t0 += D) {
+      // 1 / last of the block's windows (torch: 1.0 / last, one correctly rounded division per env and day)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int r = lr + 8 * k;
+        const float last = sP[r * SP + ((t0 + lc + H - 1) & (RING - 1))];
+        sInv[r * D + lc] = mode ? __fdiv_rn(1.0f, last) : 1.0f;
+      }
+      // the next block's D new prices, in flight through this block's days
+      const bool more = t0 + D < tend;
+      float pf[4] = {0.f, 0.f, 0.f, 0.f};
+      const int jn = t0 + H + D + lc;
+      if (more) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          pf[k] = p.prices[(size_t)min(r0 + lr + 8 * k, p.E - 1) * (size_t)p.ld + (size_t)min(jn, p.T - 1)];
+      }
+      bar();
+      const int nd = min(D, tend - t0);
+#pragma unroll 1
+      for (int d = 0; d < nd; ++d) {
+        const int t = t0 + d;
+        // ---------------------------------------------------------- P0: ring -> features (bf16)
+        // a wave builds its RPW rows one after the other, lane = column pair (2 l, 2 l + 1) of 112
+        // (columns 0 .. 127 and 128 .. 223).  Every load is unconditional (columns past the window re-read its
+        // last price) and the four ring columns of a lane are the same for all its rows: loads under per-element
+        // branches were issued one LDS round trip at a time.  The feature mode is compile-time in the body (one
+        // uniform branch per day picks the instance), and the low 64 pairs are prices only (host: H >= 128).
+        auto p0 = [&](auto mode_c) {
+          constexpr int md = decltype(mode_c)::value;
+          int rc[2][2];   // ring column of (pair jj, element q) on day t
+#pragma unroll
+          for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) rc[jj][q] = (t + min(2 * (lane + 64 * jj) + q, H - 1)) & (RING - 1);
+          float w[RPW][2][2], inv[RPW], fb[RPW], fs[RPW];
+#pragma unroll
+          for (int i = 0; i < RPW; ++i) {
+            const int r = wave * RPW + i;
+            inv[i] = sInv[r * D + d];
+            fb[i] = sFB[r];
+            fs[i] = sFS[r];
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+#pragma unroll
+              for (int q = 0; q < 2; ++q) w[i][jj][q] = sP[r * SP + rc[jj][q]];
+          }
+#pragma unroll
+          for (int i = 0; i < RPW; ++i) {
+            const int r = wave * RPW + i;
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+              const int c = 2 * (lane + 64 * jj);
+              float x[2];
+#pragma unroll
+              for (int q = 0; q < 2; ++q) {
+                const int k = c + q;
+                x[q] = feat_price(w[i][jj][q], inv[i], md);
+                if (jj == 1) {   // pairs that can reach column H: budget, shares, the constant 1, padding
+                  x[q] = k == H ? fb[i] : x[q];
+                  x[q] = k == H + 1 ? fs[i] : x[q];
+                  x[q] = k == H + 2 ? 1.0f : x[q];
+                  x[q] = k > H + 2 ? 0.0f : x[q];
+                }
+              }
+              if (c < INP) *reinterpret_cast<uint32_t*>(sX + r * SX + c) = pack_bf2(x[0], x[1]);
+            }
+          }
+        };
+        if (mode) p0(std::integral_constant<int, 1>{});
+        else p0(std::integral_constant<int, 0>{});
+        bar();
+        // ---------------------------------------------------------- P1: layer 1
+        {
+          f4v acc[MT][NET];
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int n = 0; n < NET; ++n) acc[i][n] = zero4();
+#pragma unroll
+          for (int ks = 0; ks < KS0; ++ks) {
+            s8v bf[NET];
+#pragma unroll
+            for (int n = 0; n < NET; ++n) bf[n] = lds_ld8(sX + (16 * n + l16) * SX + ks * 32 + 8 * g4);
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+              for (int n = 0; n < NET; ++n) acc[i][n] = mfma32(aW0[i][ks], bf[n], acc[i][n]);
+          }
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int n = 0; n < NET; ++n) {
+              const f4v v = acc[i][n];
+              lds_st4(sH1 + (16 * n + l16) * SH + m0 + 16 * i + 4 * g4, fmaxf(v[0], 0.f), fmaxf(v[1], 0.f),
+                      fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
+            }
+        }
+        bar();
+        // ---------------------------------------------------------- P2: layer 2 (+ b1) -> H2 (over X)
+        {
+          f4v acc[MT][NET];
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int n = 0; n < NET; ++n) acc[i][n] = zero4();
+#pragma unroll
+          for (int ks = 0; ks < KS1; ++ks) {
+            s8v bf[NET];
+#pragma unroll
+            for (int n = 0; n < NET; ++n) bf[n] = lds_ld8(sH1 + (16 * n + l16) * SH + ks * 32 + 8 * g4);
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+              for (int n = 0; n < NET; ++n) acc[i][n] = mfma32(aW1[i][ks], bf[n], acc[i][n]);
+          }
+#pragma unroll
+          for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int n = 0; n < NET; ++n) {
+              const f4v v = acc[i][n];
+              lds_st4(sH2 + (16 * n + l16) * SH + m0 + 16 * i + 4 * g4, fmaxf(v[0] + bb[i][0], 0.f),
+                      fmaxf(v[1] + bb[i][1], 0.f), fmaxf(v[2] + bb[i][2], 0.f), fmaxf(v[3] + bb[i][3], 0.f));
+            }
+        }
+        bar();
+        // ---------------------------------------------------------- P3: output, policy, trade
+        if (wave < NET) {
+          f4v acc = zero4();   // wave w: 16-env tile w; lanes g4 == 0 end up with q[0..3] of env 16 w + l16
+#pragma unroll
+          for (int ks = 0; ks < KS1; ++ks)
+            acc = mfma32(aW2[ks], lds_ld8(sH2 + (16 * wave + l16) * SH + ks * 32 + 8 * g4), acc);
+          if (g4 == 0) {
+            float q[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+              q[j] = acc[j] + b2[j];
+              if (p.output_relu) q[j] = fmaxf(q[j], 0.f);
+            }
+            int a = argmax3(q[0], q[1], q[2]);
+            if (!greedy) {
+              float u1, u2;
+              policy_draw(p.env_offset + (uint32_t)env, (unsigned long long)t, p.key0, p.key1, u1, u2, 4u);
+              a = exploits(u1, p.eps, (float)t, p.inv_ramp) ? a : random_action(u2);
+            }
+            const float v = sP[myrow * SP + ((t + H) & (RING - 1))];
+            const Holding h = trade_base(b, s, p.compat_env, p.b0, p.s0);
+            const Holding r = trade(a, h, v);
+            nbuy += r.shares > h.shares;
+            nsell += r.shares < h.shares;
+            b = r.budget;
+            s = r.shares;
+            vlast = v;
+            // tomorrow's window ends at today's trade price
+            sFB[myrow] = feat_budget(b, p.inv_b0, mode);
+            sFS[myrow] = feat_shares(s, v, p.inv_b0, mode);
+            if (live) {
+              const size_t o = (size_t)env * (size_t)p.steps + (size_t)(t - p.start);
+              if (p.tr_actions != nullptr) p.tr_actions[o] = (signed char)a;
+              if (p.tr_q != nullptr) {
+                p.tr_q[3 * o + 0] = q[0];
+                p.tr_q[3 * o + 1] = q[1];
+                p.tr_q[3 * o + 2] = q[2];
+              }
+              if (p.tr_equity != nullptr) p.tr_equity[o] = __fadd_rn(b, __fmul_rn((float)s, v));
+            }
+          }
+        }
+        bar();   // the next day's features overwrite X / H2; every read of this day's ring columns is done
+      }
+      if (more) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sP[(lr + 8 * k) * SP + (jn & (RING - 1))] = pf[k];
+        bar();
+      }
+    }
+    if (live) {
+      p.out_budget[env] = b;
+      p.out_shares[env] = s;
+      p.out_portfolio[env] = __fadd_rn(b, __fmul_rn((float)s, vlast));
+      p.out_buys[env] = nbuy;
+      p.out_sells[env] = nsell;
+    }
+  }
+}
+
+}  // namespace rollout
+}  // namespace st
+
+extern "C" int st_qrollout_lds_bytes() { return st::rollout::LDS_BYTES; }
+extern "C" int st_qrollout_day_block() { return st::rollout::D; }
+
+// grid <= 0: one workgroup per 32-env tile.  Pre-launch checks as st_qserve_launch (fixed padded dims 224 /
+// 128 / 16, H + 3 <= 224) plus H >= 128 (any layout that pads to 224 inputs has H >= 190; the feature phase
+// takes columns 0 .. 127 as prices) and the episode's bounds: days start .. start + steps - 1 need prices up
+// to index start + steps - 1 + H <= T - 1 <= ld - 1.
+extern "C" hipError_t st_qrollout_launch(const st::rollout::RolloutParams* p, int grid, hipStream_t stream) {
+  using namespace st::rollout;
+  if (p->E <= 0) return hipSuccess;
+  if (p->H < 128 || p->H + 3 > INP || p->T < p->H + 1 || p->ld < p->T || p->start < 0 || p->steps < 1 ||
+      (long long)p->start + p->steps > (long long)p->T - p->H || p->prices == nullptr || p->wq == nullptr ||
+      p->wf == nullptr || p->out_budget == nullptr || p->out_shares == nullptr || p->out_portfolio == nullptr ||
+      p->out_buys == nullptr || p->out_sells == nullptr)
+    return hipErrorInvalidValue;
+  // the dynamic-LDS limit is a per-device attribute of the function: set once on every device launched on
+  static bool attr[64] = {};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || !attr[dev]) {
+    e = hipFuncSetAttribute((const void*)qrollout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e != hipSuccess) return e;
+    if (dev >= 0 && dev < 64) attr[dev] = true;
+  }
+  const int ntiles = (p->E + C - 1) / C;
+  if (grid <= 0 || grid > ntiles) grid = ntiles;
+  hipLaunchKernelGGL(qrollout_kernel, dim3(grid), dim3(NT), LDS_BYTES, stream, *p);
+  return hipGetLastError();
+}
+
+// struct sizes of this file's launch ABI, for the host mirror's check (no HIP call)
+extern "C" int st_abi_qrollout(int* out, int n) {
+  const int sz[] = {(int)sizeof(st::rollout::RolloutParams)};
+  const int m = (int)(sizeof(sz) / sizeof(sz[0]));
+  for (int i = 0; i < n && i < m; ++i) out[i] = sz[i];
+  return m;
+}

@@ -9,6 +9,8 @@ Commands
 ``recurrent`` train the GRU(256) minute-bar DQN (BASELINE config 5) for N iterations.
 ``serve``   serve SelectionAction over HTTP from the batched GPU kernel (weights from an
             engine checkpoint or random init).
+``backtest`` what a policy (engine checkpoint or random init) would have done over a price history: a CSV
+            series or N synthetic ones, one rollout launch; prints policy vs buy-and-hold vs uniform random.
 ``config``  print the resolved configuration (JSON).
 
 Common flags: ``--preset {reference_compat,intended,flagship,flagship_stable,test}``,
@@ -31,13 +33,53 @@ def _cfg(a) -> Config:
     return cfg
 
 
+def _backtest(a, cfg: Config) -> dict:
+    """``backtest``: the policy, buy-and-hold (Buy at every step, as benchkit.buy_and_hold_returns) and a uniform
+    random policy over the same series, each as mean / std / median of final portfolio - budget and trade counts."""
+    import os
+
+    import numpy as np
+    import torch
+
+    from .data import prices as dp
+    from .serve import PolicyServer
+    from .serve.http import load_checkpoint_params
+    from .serve.rollout import result_from, simulate_actions
+    from .trainer.engine import resolve_device
+
+    if a.csv:
+        _, series = dp.sorted_series(dp.load_csv(a.csv))
+        P = series[None, :]
+    else:
+        d = cfg.data
+        P = dp.random_walk(d.length, d.start_price, d.volatility, d.seed, n_series=a.synthetic)
+    P = torch.from_numpy(np.ascontiguousarray(P, dtype=np.float32))
+    params = load_checkpoint_params(a.ckpt, averaged=a.weights == "average") if a.ckpt else None
+    srv = PolicyServer(cfg, params=params, device=resolve_device(a.device))
+    res = srv.backtest(P, trace=bool(a.trace_out))
+    e, H = cfg.env, cfg.model.history
+    steps = res.steps
+    g = torch.Generator().manual_seed(int(cfg.agent.seed))
+    base = {}
+    for name, acts in (("buy_and_hold", torch.zeros(P.shape[0], steps, dtype=torch.int8)),
+                       ("uniform_random", torch.randint(0, 3, (P.shape[0], steps), generator=g).to(torch.int8))):
+        out = simulate_actions(P, acts, history=H, budget0=e.budget, shares0=e.shares, compat=e.compat_decisions)
+        base[name] = result_from(out, e.budget, 0, steps, False).summary()
+    if a.trace_out:
+        os.makedirs(a.trace_out, exist_ok=True)
+        np.save(os.path.join(a.trace_out, "actions.npy"), res.actions.cpu().numpy())
+        np.save(os.path.join(a.trace_out, "equity.npy"), res.equity.cpu().numpy())
+    return {"series": int(P.shape[0]), "days": int(P.shape[1]), "steps": int(steps), "budget": float(e.budget),
+            "backend": srv.backend, "weights": (a.weights if a.ckpt else "init"), "policy": res.summary(), **base}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="sharetrade")
     sub = ap.add_subparsers(dest="cmd", required=True)
-    for name in ("train", "engine", "deep", "recurrent", "serve", "config"):
+    for name in ("train", "engine", "deep", "recurrent", "serve", "backtest", "config"):
         p = sub.add_parser(name)
         p.add_argument("--preset", default={"deep": "flagship", "recurrent": "recurrent",
-                                            "serve": "flagship"}.get(name, "reference_compat"))
+                                            "serve": "flagship", "backtest": "flagship"}.get(name, "reference_compat"))
         p.add_argument("--config", default=None)
         p.add_argument("--set", action="append", default=[])
         if name == "train":
@@ -101,6 +143,16 @@ def main(argv=None) -> int:
             p.add_argument("--weights", choices=["average", "live"], default="average",
                            help="with a checkpoint that keeps a Polyak average (engine.ema_decay): serve it or the "
                                 "live weights (profiles/r2_serve_eval.md: evaluate both)")
+        if name == "backtest":
+            p.add_argument("--ckpt", default=None, help="engine checkpoint file or directory (default: random init)")
+            p.add_argument("--weights", choices=["average", "live"], default="average",
+                           help="with a checkpoint that keeps a Polyak average: backtest it or the live weights")
+            src = p.add_mutually_exclusive_group(required=True)
+            src.add_argument("--csv", default=None, help="one series: `price, yyyy-MM-dd` rows (or a parsed .npz)")
+            src.add_argument("--synthetic", type=int, default=None, metavar="N",
+                             help="N random-walk series of data.length days (data.* of the config)")
+            p.add_argument("--device", default="auto")
+            p.add_argument("--trace-out", default=None, metavar="DIR", help="write actions.npy and equity.npy here")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(level=getattr(logging, cfg.log.loglevel, logging.INFO),
@@ -198,6 +250,9 @@ def main(argv=None) -> int:
             uvicorn.run(make_app(srv, bat, ckpt_root=root), host=a.host, port=a.port, log_level="warning")
         finally:
             bat.close()
+        return 0
+    if a.cmd == "backtest":
+        print(json.dumps(_backtest(a, cfg)))
         return 0
     if a.cmd == "engine":
         from .parallel import dist as D

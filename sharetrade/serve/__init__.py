@@ -2,11 +2,14 @@
 
 * :class:`PolicyServer` — resident weights, one launch per request batch, hot weight swaps;
 * :class:`DynamicBatcher` — single requests from many client threads -> server batches;
-* :class:`PolicyServingActor` — the reference's actor message API over the server.
+* :class:`PolicyServingActor` — the reference's actor message API over the server;
+* :meth:`PolicyServer.backtest` — whole episodes of a frozen policy in one launch (``csrc/qrollout.hip``,
+  :class:`RolloutKernel`, oracle :func:`reference_rollout`).
 """
 from .actor import LoadPolicy, PolicyLoaded, PolicyServingActor
 from .kernel import ServeKernel, reference_select, supported
+from .rollout import BacktestResult, RolloutKernel, RolloutParams, reference_rollout
 from .server import DynamicBatcher, PolicyServer
 
 __all__ = ["PolicyServer", "DynamicBatcher", "PolicyServingActor", "LoadPolicy", "PolicyLoaded", "ServeKernel",
-           "reference_select", "supported"]
+           "reference_select", "supported", "BacktestResult", "RolloutKernel", "RolloutParams", "reference_rollout"]

@@ -14,6 +14,7 @@ Weights can be swapped while serving (:meth:`PolicyServer.load_params`, e.g. fro
 """
 from __future__ import annotations
 
+import math
 import threading
 import time
 from concurrent.futures import Future
@@ -27,6 +28,7 @@ from ..env import trading as tr
 from ..models import qnet as qn
 from ..utils import rng
 from . import kernel as K
+from . import rollout as R
 
 ArrayLike = Union[torch.Tensor, np.ndarray, Sequence[float]]
 
@@ -66,6 +68,7 @@ class PolicyServer:
         self.batches = 0
         self.requests = 0
         self._kern = None
+        self._roll = None   # the backtest kernel's parameter block (first backtest)
         if backend == "native":
             self._kern = K.ServeKernel(self.layout, self.params, self.params_bf, history=self.H,
                                        feat_mode=tr.FEATURES[self.cfg.env.features], output_relu=m.output_relu,
@@ -135,6 +138,51 @@ class PolicyServer:
         return K.reference_select(self.params, self.layout, x, history=self.H, feat_mode=c.env.features,
                                   output_relu=m.output_relu, budget0=c.env.budget, epsilon=a.epsilon,
                                   ramp=a.ramp, key_seed=self.seed, seq=seq, steps=st)
+
+    # ---------------------------------------------------------------- backtesting
+    def backtest(self, prices: ArrayLike, *, start: int = 0, steps: Optional[int] = None,
+                 budget: Optional[ArrayLike] = None, shares: Optional[ArrayLike] = None, greedy: bool = True,
+                 trace: bool = False) -> R.BacktestResult:
+        """What the served policy does over price series [E, T] (or one series [T]): one decision and one
+        trade per day from day ``start`` for ``steps`` days (default: to the end of the series), every env
+        starting from the configured budget / shares or from ``budget`` / ``shares`` [E] (a continued
+        episode).  ``greedy=False`` draws the epsilon-greedy policy of the config (ramp on the day).  The
+        native backend runs ``csrc/qrollout.hip`` (one launch); the torch backend the oracle on the CPU."""
+        c, m, a = self.cfg, self.cfg.model, self.cfg.agent
+        P = torch.as_tensor(prices, dtype=torch.float32)
+        if P.dim() == 1:
+            P = P.view(1, -1)
+        if P.dim() != 2 or P.shape[1] < self.H + 1:
+            raise ValueError(f"price series must be [E, T] with T >= {self.H + 1}, got {tuple(P.shape)}")
+        T = int(P.shape[1])
+        n = T - self.H - int(start) if steps is None else int(steps)
+        E = int(P.shape[0])
+        b = None if budget is None else torch.as_tensor(budget, dtype=torch.float32).reshape(-1)
+        s = None if shares is None else torch.as_tensor(shares).to(torch.int32).reshape(-1)
+        if (b is not None and b.numel() != E) or (s is not None and s.numel() != E):
+            raise ValueError("one initial budget / shares entry per series")
+        with self._lock:
+            if self.backend == "native":
+                if self._roll is None:
+                    self._roll = R.RolloutKernel(self.layout, self.params, self.params_bf, history=self.H,
+                                                 feat_mode=tr.FEATURES[c.env.features], output_relu=m.output_relu,
+                                                 budget0=c.env.budget, shares0=c.env.shares,
+                                                 compat=c.env.compat_decisions, epsilon=a.epsilon, ramp=a.ramp,
+                                                 key=self.key)
+                Pd = P.to(self.device)
+                if Pd.stride(1) != 1:
+                    Pd = Pd.contiguous()
+                out = self._roll.run(Pd, start=int(start), steps=n,
+                                     budget=None if b is None else b.to(self.device).contiguous(),
+                                     shares=None if s is None else s.to(self.device).contiguous(),
+                                     greedy=greedy, trace=trace)
+            else:
+                out = R.reference_rollout(self.params.cpu(), self.layout, P.cpu(), history=self.H,
+                                          feat_mode=c.env.features, output_relu=m.output_relu,
+                                          budget0=c.env.budget, shares0=c.env.shares, compat=c.env.compat_decisions,
+                                          epsilon=math.inf if greedy else a.epsilon, ramp=a.ramp, key_seed=self.seed,
+                                          start=int(start), steps=n, budget=b, shares=s)
+        return R.result_from(out, c.env.budget, start, n, trace)
 
     def launch_into(self, x: torch.Tensor, acts: torch.Tensor, steps: Optional[torch.Tensor], seq: int,
                     q: Optional[torch.Tensor] = None) -> None:

@@ -218,6 +218,19 @@ def greedy_episode_returns(eng, world: int = 1, group=None, params: Optional[tor
     return out
 
 
+def backtest_returns(eng, params: Optional[torch.Tensor] = None) -> Dict[str, float]:
+    """The summary of :func:`greedy_episode_returns` (one rank) from the rollout kernel: the greedy policy of
+    the engine's current parameters (or ``params``) backtested over ``eng.prices`` in one launch
+    (``csrc/qrollout.hip``).  One forward per decision instead of a whole learning step, and the engine is
+    only read: no snapshot, no restore."""
+    from ..serve import PolicyServer
+
+    srv = PolicyServer(eng.cfg, params=eng.params if params is None else params, device=eng.device, backend="native")
+    res = srv.backtest(eng.prices)
+    fin = res.final_portfolio.double() - float(eng.cfg.env.budget)
+    return _reduce_returns(torch.ones_like(fin, dtype=torch.bool), fin, eng.E, 1, None, res.steps)
+
+
 def buy_and_hold_returns(eng, world: int = 1, group=None) -> Dict[str, float]:
     """The buy-and-hold baseline on the engine's own price banks, within its action space: Buy at every
     step (one share whenever the budget covers the price, as the env's Buy does), so the budget goes

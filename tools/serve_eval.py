@@ -15,6 +15,9 @@ Reported per policy: mean / population std of the final portfolios (the referenc
 uniform random policy and buy-and-hold.
 
     python tools/serve_eval.py --train-steps 12000 --envs 65536 --eval-envs 8192 -o profiles/r2_serve_eval.md
+
+``--rollout``: the served policies trade through :meth:`PolicyServer.backtest` (``csrc/qrollout.hip``, the
+whole episode of every env in one launch) instead of one ``SelectionAction`` launch per day.
 """
 from __future__ import annotations
 
@@ -56,6 +59,8 @@ def main() -> int:
     ap.add_argument("--eval-envs", type=int, default=8192)
     ap.add_argument("--phi", type=float, default=0.3)
     ap.add_argument("--ema-decay", type=float, default=0.999, help="engine.ema_decay: also serve the Polyak average")
+    ap.add_argument("--rollout", action="store_true",
+                    help="served policies: one PolicyServer.backtest launch per episode instead of one launch per day")
     ap.add_argument("-o", "--out", default=None)
     args = ap.parse_args()
 
@@ -102,16 +107,32 @@ def main() -> int:
     def hold_after_buy(rows, t):   # buy-and-hold: buy on day one, hold after
         return torch.full((rows.shape[0],), 0 if t == 0 else 2, device=dev, dtype=torch.long)
 
+    def episode(prices, pol):
+        """Final portfolios [E] (fp64): the per-day loop, or with --rollout one backtest launch for a served policy
+        (its epsilon-greedy draws are the backtest's own Philox stream: the same schedule, other draws)."""
+        roll = rolled.get(pol)
+        if args.rollout and roll is not None:
+            srv, greedy = roll
+            return srv.backtest(prices, greedy=greedy).final_portfolio.double()
+        return trade(prices, H, b0, pol)
+
+    rolled = {}
+
+    def _served(srv, greedy):
+        pol = served(srv) if greedy else served_eps(srv)
+        rolled[pol] = (srv, greedy)
+        return pol
+
     res = {}
-    pols = [("trained net, greedy (served)", served(trained))]
+    pols = [("trained net, greedy (served)", _served(trained, True))]
     if args.ema_decay > 0:
-        pols.append((f"Polyak average (decay {args.ema_decay}), greedy (served)", served(averaged)))
-    pols += [("trained net, epsilon-greedy as in training (served)", served_eps(trained)),
-             ("untrained net, greedy (served)", served(untrained)),
+        pols.append((f"Polyak average (decay {args.ema_decay}), greedy (served)", _served(averaged, True)))
+    pols += [("trained net, epsilon-greedy as in training (served)", _served(trained, False)),
+             ("untrained net, greedy (served)", _served(untrained, True)),
              ("uniform random", rand), ("buy one share, hold", hold_after_buy)]
     for name, pol in pols:
         t1 = time.perf_counter()
-        f = trade(test, H, b0, pol)
+        f = episode(test, pol)
         torch.cuda.synchronize()
         res[name] = {"mean": float(f.mean()), "std": float(f.std(unbiased=False)), "median": float(f.median()),
                      "return_pct": float((f.mean() / b0 - 1) * 100), "seconds": round(time.perf_counter() - t1, 2)}
@@ -119,7 +140,7 @@ def main() -> int:
 
     # the same greedy policy on series it was trained on (in sample): overfitting vs the exploration mix
     t1 = time.perf_counter()
-    f = trade(eng.prices[: args.eval_envs], H, b0, served(trained))
+    f = episode(eng.prices[: args.eval_envs], _served(trained, True))
     torch.cuda.synchronize()
     res["trained net, greedy, on training series (in sample)"] = {
         "mean": float(f.mean()), "std": float(f.std(unbiased=False)), "median": float(f.median()),
@@ -134,7 +155,8 @@ def main() -> int:
         f"{st['final_sum'] / max(st['episodes_done'], 1):,.0f}.",
         "",
         f"Evaluation: {args.eval_envs:,} unseen series (bank seed 101), one episode of {days:,} days from budget "
-        f"{b0:,.0f}; every day one batched `SelectionAction` launch for all envs (greedy, or epsilon-greedy with "
+        f"{b0:,.0f}; " + ("served policies: one `PolicyServer.backtest` launch per episode" if args.rollout else
+                           "every day one batched `SelectionAction` launch for all envs") + " (greedy, or epsilon-greedy with "
         f"the training schedule: exploit probability min({cfg.agent.epsilon}, day / {cfg.agent.ramp:g})).",
         "",
         "| policy | mean final portfolio (GetAvg) | std (GetStd) | median | mean return | seconds |",
