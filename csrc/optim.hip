@@ -54,8 +54,10 @@ constexpr int SLAB_CB = 32;     // bf16 slabs: parameters per column block of th
 
 // NV parameters per thread column: 4 (fp32 slabs [G][P], one float4 per row) or 8 (bf16 slabs: the
 // step kernel rounds each workgroup's fp32 partial sum once and stores it column-BLOCKED,
-// [P/128][G][128], so this workgroup's 128 columns of all G rows are one contiguous 64 KB run
-// instead of G strided 256-byte pieces; 8 bf16 = one 16-byte load per row).  The sums are fp32.
+// [P/32][G][32] (P % 32 == 0; pinned by tests/test_gpu_optim_kernel.py), so this workgroup's 128
+// columns are 4 adjacent column blocks -- one contiguous run of all G rows -- instead of G strided
+// 256-byte pieces; 8 bf16 = one 16-byte load per row, 4 such pieces per 64-byte block row).  The
+// sums are fp32.
 // tools/ubench/slab_reduce.hip measured the layouts / shapes (profiles/r1_slab_reduce.md).
 template <int NV, int RT>
 __global__ void __launch_bounds__(RT) reduce_optim_kernel(OptimParams p) {
