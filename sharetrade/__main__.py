@@ -11,6 +11,8 @@ Commands
             engine checkpoint or random init).
 ``backtest`` what a policy (engine checkpoint or random init) would have done over a price history: a CSV
             series or N synthetic ones, one rollout launch; prints policy vs buy-and-hold vs uniform random.
+            With a checkpoint of a ``recurrent`` run (or ``--policy gru``): the GRU(256) policy, greedy, on N
+            held-out synthetic minute-bar series; prints policy vs always-long vs uniform random vs flat.
 ``config``  print the resolved configuration (JSON).
 
 Common flags: ``--preset {reference_compat,intended,flagship,flagship_stable,test}``,
@@ -71,6 +73,59 @@ def _backtest(a, cfg: Config) -> dict:
         np.save(os.path.join(a.trace_out, "equity.npy"), res.equity.cpu().numpy())
     return {"series": int(P.shape[0]), "days": int(P.shape[1]), "steps": int(steps), "budget": float(e.budget),
             "backend": srv.backend, "weights": (a.weights if a.ckpt else "init"), "policy": res.summary(), **base}
+
+
+def _gru_path(a) -> bool:
+    """``backtest`` takes the GRU path with ``--policy gru`` or (``--policy auto``) a ``recurrent`` checkpoint."""
+    if a.policy != "auto":
+        return a.policy == "gru"
+    if not a.ckpt:
+        return False
+    from .serve.gru_rollout import checkpoint_kind
+
+    return checkpoint_kind(a.ckpt) == "recurrent"
+
+
+def _backtest_gru(a, cfg: Config) -> dict:
+    """``backtest`` of a GRU(256) policy on N held-out synthetic minute-bar series: the greedy policy, always
+    long (Buy on every bar), uniform random and flat, each as mean / std / median of the per-series return."""
+    import os
+
+    import numpy as np
+    import torch
+
+    from .data import minute_bars as mb
+    from .models import gru_qnet as gq
+    from .serve.gru_rollout import GruPolicy, result_from, simulate_minute_actions
+    from .trainer.engine import resolve_device
+
+    dev = resolve_device(a.device)
+    if a.ckpt:
+        pol = GruPolicy.from_checkpoint(a.ckpt, device=dev)
+    else:
+        pol = GruPolicy(gq.init_params(cfg.agent.seed), device=dev, seed=cfg.agent.seed)
+    N, ep_len = int(a.synthetic), int(a.ep_len)
+    T = int(a.bars) if a.bars else 4 * ep_len + 1
+    bars_seed = pol.seed + 1000 if a.bars_seed is None else int(a.bars_seed)
+    if dev.type == "cuda":
+        close, feat = mb.generate_gpu(N, T, dev, seed=bars_seed)
+    else:
+        c, f = mb.generate_numpy(N, T, seed=bars_seed)
+        close, feat = torch.from_numpy(c), torch.from_numpy(f).to(torch.bfloat16)
+    kw = dict(ep_len=ep_len, cost=float(a.cost))
+    res = pol.backtest(close, feat, trace=bool(a.trace_out), **kw)
+    steps = res.steps
+    base = {"uniform_random": pol.backtest(close, feat, greedy=False, epsilon=0.0, **kw).summary()}
+    for name, act in (("always_long", 0), ("flat", 1)):
+        out = simulate_minute_actions(close, torch.full((N, steps), act, dtype=torch.int8, device=close.device), **kw)
+        base[name] = result_from(out, 0, steps, ep_len, 0, res.backend, False).summary()
+    if a.trace_out:
+        os.makedirs(a.trace_out, exist_ok=True)
+        np.save(os.path.join(a.trace_out, "actions.npy"), res.actions.cpu().numpy())
+        np.save(os.path.join(a.trace_out, "reward.npy"), res.reward.cpu().numpy())
+    return {"policy_kind": "gru", "series": N, "bars": T, "steps": int(steps), "ep_len": ep_len, "cost": float(a.cost),
+            "bars_seed": bars_seed, "backend": res.backend, "weights": "checkpoint" if a.ckpt else "init",
+            "policy": res.summary(), **base}
 
 
 def main(argv=None) -> int:
@@ -152,7 +207,16 @@ def main(argv=None) -> int:
             src.add_argument("--synthetic", type=int, default=None, metavar="N",
                              help="N random-walk series of data.length days (data.* of the config)")
             p.add_argument("--device", default="auto")
-            p.add_argument("--trace-out", default=None, metavar="DIR", help="write actions.npy and equity.npy here")
+            p.add_argument("--trace-out", default=None, metavar="DIR",
+                           help="write actions.npy and equity.npy (GRU policy: reward.npy) here")
+            p.add_argument("--policy", choices=["auto", "mlp", "gru"], default="auto",
+                           help="auto: the GRU(256) path for a checkpoint of a `recurrent` run, else the MLP path")
+            p.add_argument("--bars", type=int, default=None, metavar="T",
+                           help="GRU policy: bars per synthetic series (default 4 episodes + 1)")
+            p.add_argument("--bars-seed", type=int, default=None, metavar="S",
+                           help="GRU policy: seed of the synthetic bars (default: the policy's seed + 1000, held out)")
+            p.add_argument("--ep-len", type=int, default=390, help="GRU policy: bars per episode")
+            p.add_argument("--cost", type=float, default=0.01, help="GRU policy: cost per position change")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(level=getattr(logging, cfg.log.loglevel, logging.INFO),
@@ -252,6 +316,12 @@ def main(argv=None) -> int:
             bat.close()
         return 0
     if a.cmd == "backtest":
+        if _gru_path(a):
+            if a.csv:
+                ap.error("backtest of a GRU policy: --csv is not supported (the CSV format has no bar features); "
+                         "use --synthetic N")
+            print(json.dumps(_backtest_gru(a, cfg)))
+            return 0
         print(json.dumps(_backtest(a, cfg)))
         return 0
     if a.cmd == "engine":

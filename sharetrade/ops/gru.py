@@ -57,6 +57,19 @@ class ActArgs(C.Structure):
                 ("done_ctr", C.c_void_p)]
 
 
+class RolloutArgs(C.Structure):
+    """``GruRollout`` of ``csrc/gru_rollout.hip``: a frozen policy over bars start .. start + steps - 1."""
+    _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
+                ("wq", C.c_void_p), ("feat", C.c_void_p), ("close", C.c_void_p), ("ret", C.c_void_p),
+                ("h0", C.c_void_p), ("position", C.c_void_p), ("entry", C.c_void_p),
+                ("out_ret", C.c_void_p), ("out_trades", C.c_void_p), ("out_long", C.c_void_p),
+                ("out_position", C.c_void_p), ("out_entry", C.c_void_p), ("out_h", C.c_void_p),
+                ("tr_actions", C.c_void_p), ("tr_q", C.c_void_p), ("tr_reward", C.c_void_p),
+                ("E", C.c_int), ("T", C.c_int), ("start", C.c_int), ("steps", C.c_int), ("origin", C.c_int),
+                ("ep_len", C.c_int), ("eps", C.c_float), ("cost", C.c_float), ("inv_ep_len", C.c_float),
+                ("key0", C.c_uint32), ("key1", C.c_uint32), ("env_offset", C.c_uint32)]
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("rx", C.c_void_p), ("ra", C.c_void_p), ("rr", C.c_void_p), ("rd", C.c_void_p), ("rh0", C.c_void_p),
                 ("rctrl", C.c_void_p), ("cap", C.c_int), ("S", C.c_int), ("B", C.c_int), ("key0", C.c_uint32),
@@ -95,6 +108,7 @@ def lib():
                          ("st_gru_pack", [C.POINTER(PackArgs), vp]),
                          ("st_gru_act", [C.POINTER(ActArgs), i, vp]),
                          ("st_gru_act_pair", [C.POINTER(ActArgs), i, vp]),
+                         ("st_gru_rollout_launch", [C.POINTER(RolloutArgs), i, vp]),
                          ("st_gru_gather", [C.POINTER(GatherArgs), vp]),
                          ("st_gru_seq_fwd", [C.POINTER(SeqFwdArgs), vp]),
                          ("st_gru_td", [C.POINTER(TDArgs), vp]),
@@ -106,6 +120,8 @@ def lib():
             f.restype = C.c_int
         L.st_gru_act_lds_bytes.restype = C.c_int
         L.st_gru_act_pair_smax.restype = C.c_int
+        L.st_gru_rollout_lds_bytes.restype = C.c_int
+        L.st_gru_rollout_block.restype = C.c_int
         L._gru_bound = True
     return L
 

@@ -4,12 +4,16 @@
 * :class:`DynamicBatcher` — single requests from many client threads -> server batches;
 * :class:`PolicyServingActor` — the reference's actor message API over the server;
 * :meth:`PolicyServer.backtest` — whole episodes of a frozen policy in one launch (``csrc/qrollout.hip``,
-  :class:`RolloutKernel`, oracle :func:`reference_rollout`).
+  :class:`RolloutKernel`, oracle :func:`reference_rollout`);
+* :class:`GruPolicy` — a frozen GRU(256) policy of config 5 and its backtest on minute bars
+  (``csrc/gru_rollout.hip``, oracle :func:`reference_gru_rollout`).
 """
 from .actor import LoadPolicy, PolicyLoaded, PolicyServingActor
+from .gru_rollout import GruBacktestResult, GruPolicy, reference_gru_rollout, simulate_minute_actions
 from .kernel import ServeKernel, reference_select, supported
 from .rollout import BacktestResult, RolloutKernel, RolloutParams, reference_rollout
 from .server import DynamicBatcher, PolicyServer
 
 __all__ = ["PolicyServer", "DynamicBatcher", "PolicyServingActor", "LoadPolicy", "PolicyLoaded", "ServeKernel",
-           "reference_select", "supported", "BacktestResult", "RolloutKernel", "RolloutParams", "reference_rollout"]
+           "reference_select", "supported", "BacktestResult", "RolloutKernel", "RolloutParams", "reference_rollout",
+           "GruPolicy", "GruBacktestResult", "reference_gru_rollout", "simulate_minute_actions"]

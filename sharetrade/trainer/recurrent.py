@@ -534,6 +534,23 @@ class RecurrentDQN:
         for _ in range(updates):
             self.update_step()
 
+    # ---------------------------------------------------------------- held-out evaluation
+    def backtest(self, close: Optional[torch.Tensor] = None, feat: Optional[torch.Tensor] = None, *,
+                 envs: int = 4096, bars: Optional[int] = None, net: str = "online", **kw):
+        """The current online (or target) net, frozen and greedy, over whole episodes of bars it was not trained
+        on: by default ``envs`` series of ``bars`` (default 4 episodes + 1) bars from the generator's seed
+        ``seed + 1000``.  One launch of ``csrc/gru_rollout.hip``; reads the parameters and touches none of the
+        learner's state (envs, replay, recurrent state, counters).  ``kw`` goes to ``GruPolicy.backtest``."""
+        from ..serve.gru_rollout import GruPolicy
+
+        pol = GruPolicy.from_learner(self, net=net)
+        if close is None:
+            T = 4 * self.ep_len + 1 if bars is None else int(bars)
+            close, feat = mb.generate_gpu(int(envs), T, self.dev, self.bp, seed=self.seed + 1000)
+        kw.setdefault("ep_len", self.ep_len)
+        kw.setdefault("cost", self.cost)
+        return pol.backtest(close, feat, **kw)
+
     # ---------------------------------------------------------------- checkpoint / resume
     _STATE_KEYS = ("flat", "mflat", "vflat", "tflat", "opt_ctrl", "h", "pos", "ep_start", "position", "entry",
                    "ep_ret", "episodes", "last_ret", "rx", "ra", "rr", "rd", "rh0", "rctrl", "ctrl", "stats", "loss")
