@@ -8,7 +8,8 @@ Commands
 ``deep``    train the 4x1024-MLP replay DQN (BASELINE config 4) for N iterations.
 ``recurrent`` train the GRU(256) minute-bar DQN (BASELINE config 5) for N iterations.
 ``serve``   serve SelectionAction over HTTP from the batched GPU kernel (weights from an
-            engine checkpoint or random init).
+            engine checkpoint or random init).  With a checkpoint of a ``recurrent`` run (or ``--policy gru``):
+            stateful GRU(256) sessions, one minute bar per request (``/session`` routes).
 ``backtest`` what a policy (engine checkpoint or random init) would have done over a price history: a CSV
             series or N synthetic ones, one rollout launch; prints policy vs buy-and-hold vs uniform random.
             With a checkpoint of a ``recurrent`` run (or ``--policy gru``): the GRU(256) policy, greedy, on N
@@ -76,7 +77,8 @@ def _backtest(a, cfg: Config) -> dict:
 
 
 def _gru_path(a) -> bool:
-    """``backtest`` takes the GRU path with ``--policy gru`` or (``--policy auto``) a ``recurrent`` checkpoint."""
+    """``backtest`` and ``serve`` take the GRU path with ``--policy gru`` or (``--policy auto``) a ``recurrent``
+    checkpoint."""
     if a.policy != "auto":
         return a.policy == "gru"
     if not a.ckpt:
@@ -198,6 +200,11 @@ def main(argv=None) -> int:
             p.add_argument("--weights", choices=["average", "live"], default="average",
                            help="with a checkpoint that keeps a Polyak average (engine.ema_decay): serve it or the "
                                 "live weights (profiles/r2_serve_eval.md: evaluate both)")
+            p.add_argument("--policy", choices=["auto", "mlp", "gru"], default="auto",
+                           help="auto: GRU(256) sessions for a checkpoint of a `recurrent` run, else the MLP routes")
+            p.add_argument("--max-sessions", type=int, default=65536, help="GRU policy: slots of the session table")
+            p.add_argument("--ep-len", type=int, default=390, help="GRU policy: bars per episode")
+            p.add_argument("--cost", type=float, default=0.01, help="GRU policy: cost per position change")
         if name == "backtest":
             p.add_argument("--ckpt", default=None, help="engine checkpoint file or directory (default: random init)")
             p.add_argument("--weights", choices=["average", "live"], default="average",
@@ -303,6 +310,22 @@ def main(argv=None) -> int:
         from .serve.http import load_checkpoint_params, make_app
         from .trainer.engine import resolve_device
 
+        if _gru_path(a):
+            from .models import gru_qnet as gq
+            from .serve.gru_rollout import GruPolicy
+            from .serve.gru_serve import GruBatcher, GruSessionServer
+            from .serve.http import make_gru_app
+
+            dev = resolve_device(a.device)
+            pol = GruPolicy.from_checkpoint(a.ckpt, device=dev) if a.ckpt else \
+                GruPolicy(gq.init_params(cfg.agent.seed), device=dev, seed=cfg.agent.seed)
+            gsrv = GruSessionServer(pol, a.max_sessions, ep_len=a.ep_len, cost=a.cost)
+            gbat = GruBatcher(gsrv, max_batch=a.max_batch, max_delay_us=a.max_delay_us)
+            try:
+                uvicorn.run(make_gru_app(gsrv, gbat), host=a.host, port=a.port, log_level="warning")
+            finally:
+                gbat.close()
+            return 0
         params = load_checkpoint_params(a.ckpt, averaged=a.weights == "average") if a.ckpt else None
         srv = PolicyServer(cfg, params=params, device=resolve_device(a.device))
         bat = DynamicBatcher(srv, max_batch=a.max_batch, max_delay_us=a.max_delay_us)

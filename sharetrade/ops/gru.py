@@ -70,6 +70,29 @@ class RolloutArgs(C.Structure):
                 ("key0", C.c_uint32), ("key1", C.c_uint32), ("env_offset", C.c_uint32)]
 
 
+class ServeArgs(C.Structure):
+    """``GruServe`` of ``csrc/gru_serve.hip``: B request rows, one bar each, on a table of S session slots."""
+    _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
+                ("wq", C.c_void_p), ("slot", C.c_void_p), ("feat", C.c_void_p), ("close", C.c_void_p),
+                ("flags", C.c_void_p), ("h", C.c_void_p), ("rec", C.c_void_p), ("action", C.c_void_p),
+                ("position", C.c_void_p), ("reward", C.c_void_p), ("q", C.c_void_p),
+                ("B", C.c_int), ("S", C.c_int), ("ep_len", C.c_int), ("eps", C.c_float), ("cost", C.c_float),
+                ("inv_ep_len", C.c_float), ("key0", C.c_uint32), ("key1", C.c_uint32)]
+
+
+class ServeRec(C.Structure):
+    """The scalar record of a session slot (``ServeRec`` of ``csrc/gru_serve.hip``): the first words of a
+    ``SERVE_REC_WORDS``-dword row of the table's ``rec`` tensor."""
+    _fields_ = [("position", C.c_int), ("entry", C.c_float), ("elapsed", C.c_int), ("last_close", C.c_float),
+                ("pend_pos", C.c_int), ("pend_fee", C.c_float), ("ret", C.c_float), ("trades", C.c_int),
+                ("long", C.c_int), ("bars", C.c_uint32), ("draw_id", C.c_uint32)]
+
+
+SERVE_REC_WORDS = 16
+SERVE_REC_COLS = {n: i for i, (n, _) in enumerate(ServeRec._fields_)}
+SERVE_REC_FLOAT = frozenset(n for n, t in ServeRec._fields_ if t is C.c_float)
+
+
 class GatherArgs(C.Structure):
     _fields_ = [("rx", C.c_void_p), ("ra", C.c_void_p), ("rr", C.c_void_p), ("rd", C.c_void_p), ("rh0", C.c_void_p),
                 ("rctrl", C.c_void_p), ("cap", C.c_int), ("S", C.c_int), ("B", C.c_int), ("key0", C.c_uint32),
@@ -109,6 +132,7 @@ def lib():
                          ("st_gru_act", [C.POINTER(ActArgs), i, vp]),
                          ("st_gru_act_pair", [C.POINTER(ActArgs), i, vp]),
                          ("st_gru_rollout_launch", [C.POINTER(RolloutArgs), i, vp]),
+                         ("st_gru_serve_launch", [C.POINTER(ServeArgs), i, vp]),
                          ("st_gru_gather", [C.POINTER(GatherArgs), vp]),
                          ("st_gru_seq_fwd", [C.POINTER(SeqFwdArgs), vp]),
                          ("st_gru_td", [C.POINTER(TDArgs), vp]),
@@ -122,6 +146,9 @@ def lib():
         L.st_gru_act_pair_smax.restype = C.c_int
         L.st_gru_rollout_lds_bytes.restype = C.c_int
         L.st_gru_rollout_block.restype = C.c_int
+        L.st_gru_serve_lds_bytes.restype = C.c_int
+        L.st_abi_gru_serve.argtypes = [C.POINTER(C.c_int), i]
+        L.st_abi_gru_serve.restype = C.c_int
         L._gru_bound = True
     return L
 

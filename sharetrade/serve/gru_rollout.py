@@ -149,6 +149,57 @@ def simulate_minute_actions(close: torch.Tensor, actions: torch.Tensor, *, start
             "reward": reward}
 
 
+class GruBarNet:
+    """The net arithmetic of one bar, shared by :func:`reference_gru_rollout` and the serving oracle
+    (``serve/gru_serve.py::reference_gru_serve``): the weights prepared once (gate pre-scale, rounding points
+    ``pts`` emulated), then ``bar(x, h) -> (h', q)`` on fp32 x rows [N, 12] and the state ``h`` [N, 256]."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], pts, dtype: torch.dtype, dev):
+        H = gq.HID
+        bf = self.bf
+        self.pts, self.dtype = pts, dtype
+        P = {n: params[n].detach().to(dev).float().reshape(_shapes()[n]) for n in PARAM_NAMES}
+        # the packed weights carry the gate pre-scale (gru_pack_kernel): fp32 product, then the rounding; the
+        # gates are evaluated on the pre-scaled pre-activations as 1 / (1 + 2^y) and 2 / (1 + 2^y) - 1
+        gs = G.gate_prescale().to(dev)
+        wih = P["w_ih"][:, :gq.X_ACT] * gs[:, None]
+        whh = P["w_hh"] * gs[:, None]
+        self.Wih = (bf(wih) if "w_ih" in pts else wih).to(dtype)
+        self.Whh = (G.mx_roundtrip(whh) if "w_hh" in pts else whh).to(dtype)
+        self.b_rz = ((P["b_ih"] + P["b_hh"])[:2 * H] * G.GS_RZ).to(dtype)
+        self.b_in = (P["b_ih"][2 * H:] * G.GS_N).to(dtype)
+        self.b_hn = (P["b_hh"][2 * H:] * G.GS_N).to(dtype)
+        self.Wq = (bf(P["w_q"]) if "q" in pts else P["w_q"]).to(dtype)
+        self.bq = P["b_q"].to(dtype)
+
+    @staticmethod
+    def bf(v: torch.Tensor) -> torch.Tensor:
+        return v.float().to(torch.bfloat16).float()
+
+    def bar(self, x: torch.Tensor, h: torch.Tensor):
+        H, pts, dtype, bf = gq.HID, self.pts, self.dtype, self.bf
+        b_rz, b_in, b_hn = self.b_rz, self.b_in, self.b_hn
+        x = (bf(x) if "x" in pts else x).to(dtype)
+        hq = G.mx_roundtrip(h.float()).to(dtype) if "h" in pts else h   # (the kernel's state is fp32)
+        gx = x @ self.Wih[:, :x.shape[1]].t()
+        gh = hq @ self.Whh.t()
+        r = 1.0 / (1.0 + torch.exp2(gx[:, :H] + gh[:, :H] + b_rz[:H]))
+        z = 1.0 / (1.0 + torch.exp2(gx[:, H:2 * H] + gh[:, H:2 * H] + b_rz[H:]))
+        n = 2.0 / (1.0 + torch.exp2(r * (gh[:, 2 * H:] + b_hn) + (gx[:, 2 * H:] + b_in))) - 1.0
+        h = z * (h - n) + n
+        hb = (bf(h) if "q" in pts else h.float()).to(dtype)
+        q = (hb @ self.Wq.t() + self.bq).float()
+        return h, q
+
+
+def rounding_points(emulate: Union[bool, Iterable[str]]) -> set:
+    """The ``emulate=`` switch of the oracles as a set of names from ``ROUNDING_POINTS``."""
+    pts = set(ROUNDING_POINTS) if emulate is True else set() if emulate is False else set(emulate)
+    if not pts <= ROUNDING_POINTS:
+        raise ValueError(f"unknown rounding points {sorted(pts - ROUNDING_POINTS)}")
+    return pts
+
+
 def reference_gru_rollout(params: Dict[str, torch.Tensor], close: torch.Tensor, feat: torch.Tensor, *,
                           start: int = 0, steps: Optional[int] = None, ep_len: int = 390, cost: float = 0.01,
                           origin: Optional[int] = None, epsilon: float = math.inf, seed: int = 0,
@@ -168,9 +219,7 @@ def reference_gru_rollout(params: Dict[str, torch.Tensor], close: torch.Tensor, 
     ``h`` MX-fp8 of the fp32 state entering the recurrent product; ``q`` bf16 h' and bf16 W_q in the Q head.
     ``emulate=False`` is the plain GRU cell.  ``forced_actions`` [E, steps] replaces the policy's choice
     (``q`` is still the net's); ``epsilon = inf`` is greedy."""
-    pts = set(ROUNDING_POINTS) if emulate is True else set() if emulate is False else set(emulate)
-    if not pts <= ROUNDING_POINTS:
-        raise ValueError(f"unknown rounding points {sorted(pts - ROUNDING_POINTS)}")
+    pts = rounding_points(emulate)
     Cl = close.float()
     E, T = Cl.shape
     dev = Cl.device
@@ -178,21 +227,7 @@ def reference_gru_rollout(params: Dict[str, torch.Tensor], close: torch.Tensor, 
     F = feat.to(dev).float()
     R = mb.bar_returns(Cl) if ret is None else ret.to(dev, torch.float32)
     H = gq.HID
-    bf = lambda v: v.float().to(torch.bfloat16).float()
-    P = {n: params[n].detach().to(dev).float().reshape(_shapes()[n]) for n in PARAM_NAMES}
-    # the packed weights carry the gate pre-scale (gru_pack_kernel): fp32 product, then the rounding; the
-    # gates are evaluated on the pre-scaled pre-activations as 1 / (1 + 2^y) and 2 / (1 + 2^y) - 1
-    gs = G.gate_prescale().to(dev)
-    wih = P["w_ih"][:, :gq.X_ACT] * gs[:, None]
-    whh = P["w_hh"] * gs[:, None]
-    Wih = (bf(wih) if "w_ih" in pts else wih).to(dtype)
-    Whh = (G.mx_roundtrip(whh) if "w_hh" in pts else whh).to(dtype)
-    b_rz = ((P["b_ih"] + P["b_hh"])[:2 * H] * G.GS_RZ).to(dtype)
-    b_in = (P["b_ih"][2 * H:] * G.GS_N).to(dtype)
-    b_hn = (P["b_hh"][2 * H:] * G.GS_N).to(dtype)
-    Wq = (bf(P["w_q"]) if "q" in pts else P["w_q"]).to(dtype)
-    bq = P["b_q"].to(dtype)
-
+    net = GruBarNet(params, pts, dtype, dev)
     env = _Env(E, cost, position, entry, dev)
     h = torch.zeros(E, H, dtype=dtype, device=dev) if h0 is None else h0.to(dev, torch.float32).to(dtype).clone()
     ids = (np.arange(E, dtype=np.uint64) + np.uint64(int(env_offset) & 0xFFFFFFFF)).astype(np.uint32)
@@ -205,16 +240,7 @@ def reference_gru_rollout(params: Dict[str, torch.Tensor], close: torch.Tensor, 
         t = start + i
         done = (t + 1 - es) >= ep_len
         x = torch.cat([F[:, t], env.x_env(Cl[:, t], t - es, inv_ep_len)], dim=1)
-        x = (bf(x) if "x" in pts else x).to(dtype)
-        hq = G.mx_roundtrip(h.float()).to(dtype) if "h" in pts else h   # (the kernel's state is fp32)
-        gx = x @ Wih[:, :x.shape[1]].t()
-        gh = hq @ Whh.t()
-        r = 1.0 / (1.0 + torch.exp2(gx[:, :H] + gh[:, :H] + b_rz[:H]))
-        z = 1.0 / (1.0 + torch.exp2(gx[:, H:2 * H] + gh[:, H:2 * H] + b_rz[H:]))
-        n = 2.0 / (1.0 + torch.exp2(r * (gh[:, 2 * H:] + b_hn) + (gx[:, 2 * H:] + b_in))) - 1.0
-        h = z * (h - n) + n
-        hb = (bf(h) if "q" in pts else h.float()).to(dtype)
-        q = (hb @ Wq.t() + bq).float()
+        h, q = net.bar(x, h)
         a = policy_actions(torch.argmax(q, dim=1), seed, ids, t, float(epsilon))   # first max on ties
         if forced_actions is not None:
             a = forced_actions[:, i].to(dev).long()

@@ -17,6 +17,17 @@ Routes (JSON):
 * ``GET /health`` -> backend, device, served batches / requests;
 * ``GET /metrics`` -> Prometheus text format: requests / batches / errors per route, request latency
   histogram, batch-size histogram of the dynamic batcher (one registry per app).
+
+A GRU(256) policy (:func:`make_gru_app`, a ``recurrent`` checkpoint) is served through sessions instead, the
+recurrent state living on the GPU between requests (``serve/gru_serve.py``):
+
+* ``POST /session`` -> ``{"session": id}`` opens a session;
+* ``POST /session/{id}/bar`` ``{"features": [8 floats], "close": c, "new_episode": false}`` ->
+  ``{"action": "Buy"|"Sell"|"Hold", "index": i, "position": 0|1, "reward": r}`` -- the session's next minute bar,
+  grouped with concurrent calls by the :class:`GruBatcher`; ``reward`` is the realised reward of the session's
+  previous bar;
+* ``GET /session/{id}`` -> the session's scalar state; ``DELETE /session/{id}`` closes it;
+* ``GET /health`` and ``GET /metrics`` (bars served, latency and batch-size histograms).
 """
 from __future__ import annotations
 
@@ -204,6 +215,97 @@ def make_app(server: PolicyServer, batcher: Optional[DynamicBatcher] = None, ckp
     @app.get("/metrics")
     def metrics():
         _batch_sizes()
+        return Response(generate_latest(reg), media_type=CONTENT_TYPE_LATEST)
+
+    return app
+
+
+class BarReq(BaseModel):
+    features: List[float]
+    close: float
+    new_episode: bool = False
+
+
+def make_gru_app(server, batcher=None):
+    """The session routes of a :class:`~sharetrade.serve.gru_serve.GruSessionServer`; bars go through
+    ``batcher`` (a :class:`~sharetrade.serve.gru_serve.GruBatcher`) when there is one."""
+    from fastapi import FastAPI, HTTPException
+    from fastapi.responses import Response
+    from prometheus_client import CONTENT_TYPE_LATEST, CollectorRegistry, Counter, Gauge, Histogram, generate_latest
+
+    from ..data import minute_bars as mb
+
+    app = FastAPI(title="sharetrade GRU session server")
+    reg = CollectorRegistry()
+    m_bars = Counter("sharetrade_gru_bars", "bars served", registry=reg)
+    m_err = Counter("sharetrade_gru_errors", "rejected calls", ["route"], registry=reg)
+    m_open = Gauge("sharetrade_gru_sessions", "open sessions", registry=reg)
+    m_lat = Histogram("sharetrade_gru_latency_seconds", "bar latency", registry=reg,
+                      buckets=(1e-4, 2.5e-4, 5e-4, 1e-3, 2.5e-3, 5e-3, 1e-2, 2.5e-2, 1e-1, 1.0))
+    m_bs = Histogram("sharetrade_gru_batch_rows", "rows per kernel launch (batcher)", registry=reg,
+                     buckets=(1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 4096, 16384))
+    seen = {"batches": 0}
+
+    def _known(sid: int, route: str) -> None:
+        if not server.is_open(sid):
+            m_err.labels(route).inc()
+            raise HTTPException(404, f"no open session {sid}")
+
+    @app.post("/session")
+    def open_session():
+        try:
+            sid = server.open(1)[0]
+        except RuntimeError as e:
+            m_err.labels("open").inc()
+            raise HTTPException(503, str(e))
+        m_open.inc()
+        return {"session": int(sid)}
+
+    @app.post("/session/{sid}/bar")
+    async def bar(sid: int, req: BarReq):
+        t0 = time.perf_counter()
+        _known(sid, "bar")
+        if len(req.features) != mb.NFEAT:
+            m_err.labels("bar").inc()
+            raise HTTPException(400, f"a bar holds {mb.NFEAT} features, got {len(req.features)}")
+        try:
+            if batcher is not None:
+                a, pos, rew = await asyncio.wrap_future(batcher.submit(sid, req.features, req.close, req.new_episode))
+            else:
+                d = await asyncio.to_thread(server.step, [sid], [req.features], [req.close], [req.new_episode])
+                a, pos, rew = int(d.actions.cpu()[0]), int(d.position.cpu()[0]), float(d.reward.cpu()[0])
+        except ValueError as e:
+            m_err.labels("bar").inc()
+            raise HTTPException(409, str(e))
+        m_bars.inc()
+        m_lat.observe(time.perf_counter() - t0)
+        return {"action": repr(action_of(a)), "index": int(a), "position": int(pos), "reward": float(rew)}
+
+    @app.get("/session/{sid}")
+    def session_state(sid: int):
+        _known(sid, "state")
+        st = server.state([sid])
+        return {"session": sid, **{k: v.cpu()[0].item() for k, v in st.items() if k != "h"}}
+
+    @app.delete("/session/{sid}")
+    def close_session(sid: int):
+        _known(sid, "close")
+        server.close([sid])
+        m_open.dec()
+        return {"closed": sid}
+
+    @app.get("/health")
+    def health():
+        return {"policy": "gru", "backend": server.backend, "device": str(server.device), "batches": server.batches,
+                "bars": server.bars_served, "sessions": int(server._open.sum()), "max_sessions": server.S}
+
+    @app.get("/metrics")
+    def metrics():
+        if batcher is not None:
+            bs = batcher.batch_sizes
+            for n in bs[seen["batches"]:len(bs)]:
+                m_bs.observe(n)
+            seen["batches"] = len(bs)
         return Response(generate_latest(reg), media_type=CONTENT_TYPE_LATEST)
 
     return app
