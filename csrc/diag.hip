@@ -6,7 +6,10 @@
 // single GPU: `grid` workgroups, each holding 4 KiB of LDS for `usec` microseconds (s_memrealtime,
 // 100 MHz), so tools/overlap_rehearsal.py can time the static vs dynamic chunk schedule with k CUs
 // taken away for T us per step.  Bounded: every wave exits after usec (or 2^24 polls).
-#include "common.h"
+//
+// And the table behind the ws step kernel's tick reciprocal (csrc/qstep.h tick_rcp): for every tick 1 .. 65,535
+// the bits of the IEEE division and of tick_rcp, for the test that proves them equal.
+#include "qstep.h"
 
 namespace st {
 
@@ -24,7 +27,23 @@ __global__ void __launch_bounds__(64) occupy_kernel(int usec, int* sink) {
   if (threadIdx.x == 0 && hold[63] == -1) sink[blockIdx.x] = polls;   // keeps `hold` live
 }
 
+// out_div[x - 1] = bits of __fdiv_rn(1, x), out_rcp[x - 1] = bits of tick_rcp(x), x = 1 .. 65,535
+__global__ void __launch_bounds__(256) tick_rcp_table_kernel(unsigned* out_div, unsigned* out_rcp) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 65535) return;
+  const float x = (float)(i + 1);
+  out_div[i] = __float_as_uint(__fdiv_rn(1.0f, x));
+  out_rcp[i] = __float_as_uint(tick_rcp(x));
+}
+
 }  // namespace st
+
+// both outputs: 65,535 words
+extern "C" hipError_t st_tick_rcp_table(unsigned* out_div, unsigned* out_rcp, hipStream_t stream) {
+  if (out_div == nullptr || out_rcp == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(st::tick_rcp_table_kernel, dim3(256), dim3(256), 0, stream, out_div, out_rcp);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t st_occupy(int grid, int usec, int* sink, hipStream_t stream) {
   if (grid < 1 || grid > 4096 || usec < 0 || usec > 100000) return hipErrorInvalidValue;

@@ -176,5 +176,15 @@ ST_DEV float4 ldu4(const float* a) {
   __builtin_memcpy(&v, a, sizeof(v));
   return v;
 }
+// 1 / x for a 16-bit tick x (an integer 1 .. 65,535 held as a float): v_rcp_f32 (within 1 ulp), one fma for the
+// exact residual 1 - x r and one for the correction.  In this range nothing under- or overflows, so the scaling
+// and fix-up steps of the IEEE division sequence (v_div_scale / v_div_fmas / v_div_fixup, ~12 dependent
+// instructions) never act; the result equals __fdiv_rn(1.0f, x) bit for bit for every tick
+// (tests/test_gpu_ws_latency_items.py checks all 65,535 through csrc/diag.hip tick_rcp_table).
+ST_DEV float tick_rcp(float x) {
+  const float r = __builtin_amdgcn_rcpf(x);
+  const float e = __fmaf_rn(-x, r, 1.0f);
+  return __fmaf_rn(e, r, r);
+}
 
 }  // namespace st

@@ -61,9 +61,37 @@
 //  - Q(x)'s first WS_L2PRE layer-2 W1 fragments are read before the slot claim;
 //  - gradient waves take ring slots in pairs (K = 32 weight-gradient MFMAs; single slots: 3.4 % slower), the
 //    data waves form dZ2 (gradient waves forming it: 13 % slower), no issue priorities (gradient priority: +25 %).
+// Fixed latencies taken off the two chains (profiles/ws_latency_items.md; each a macro, 0 = the form before it,
+// buildable as csrc/ab/qstep_ws_<item>0.hip; none changes a rounding point, an MFMA operand or a summation order):
+//  - WS_L2NPRE: Q(x')'s first layer-2 W1 fragments are read after Q(x)'s output MFMAs, under the epsilon-greedy
+//    draw and the env step (the registers of X, X' and H2 are dead there), as WS_L2PRE does for Q(x);
+//  - WS_GW1PRE: the gradient waves' W1^T fragments of dZ1 depend on nothing in a slot: those of the first
+//    WS_GW1PRE k-steps are read before the wait for the slot pair and land under it.  2 of the 4 k-steps (16
+//    VGPRs, the kernel stays at 246) is 1.4 % faster than none; all 4 take the kernel to 256 VGPRs and tie with
+//    none, 1 and 3 lie between; resident fragments do not fit beside the 188 accumulator VGPRs;
+//  - WS_TICK_RCP (tick bank): 1 / last and 1 / next as v_rcp_f32 + one residual / correction fma pair, equal to
+//    the IEEE division for every tick (csrc/qstep.h tick_rcp); WS_TICK_HOIST: the next tile's reciprocals formed
+//    at the end of the tile, once the window's first load has landed, so the features start with their multiplies;
+//  - WS_EARLY_LOADS: tile 0's env-state loads are issued before the weight-image DMA and its price windows right
+//    after it (two HBM round trips per launch under the image copy; the gather prologue keeps its order).
 constexpr int WS_GXP = 2;       // paired slots: X fragment pairs read this many dW0 steps ahead
 #ifndef WS_L2PRE
 #define WS_L2PRE 4
+#endif
+#ifndef WS_L2NPRE
+#define WS_L2NPRE 4
+#endif
+#ifndef WS_GW1PRE
+#define WS_GW1PRE 2
+#endif
+#ifndef WS_TICK_RCP
+#define WS_TICK_RCP 1
+#endif
+#ifndef WS_TICK_HOIST
+#define WS_TICK_HOIST 1
+#endif
+#ifndef WS_EARLY_LOADS
+#define WS_EARLY_LOADS 1
 #endif
 #ifndef WS_WAIT_UNROLL
 #define WS_WAIT_UNROLL -1 // ring-wait poll loops: 0 not unrolled, > 0 unrolled by this count, -1 the compiler's
@@ -279,60 +307,10 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
     return c < nchunks ? c : -1;
   };
 
-  // ------------------------------------------------------------------ prologue: weight images, ring state
-#if defined(WS_PROLOGUE_REPS) && WS_PROLOGUE_REPS > 1   // timing build csrc/ab/qstep_ws_pro2.hip: images built twice
-  for (int rep_ = 0; rep_ < WS_PROLOGUE_REPS; ++rep_) {
-    __syncthreads();
-#else
-  {
-#endif
-   if (p.wimg != nullptr) {
-    // the images as one 87,872-byte run (oW0 .. oSLOT, built by the optimizer pass): 16 bytes per lane and
-    // LDS-DMA instruction, 11 per wave, all in flight at once (the gather below takes ~10 us per launch:
-    // profiles/r5_ws_prologue.md)
-    constexpr int NCH = (oSLOT - oW0) / 16;
-    for (int j = wave; j * 64 < NCH; j += NT / 64) {
-      const int c = j * 64 + lane;
-      if (c < NCH)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.wimg + 16 * c),
-                                         (__attribute__((address_space(3))) void*)(smem + oW0 + 1024 * j), 16, 0, 0);
-    }
-    __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): this wave's copies landed (the barrier below joins the waves)
-   } else {
-    const bf16_t* w0 = p.wq + p.off_w0;
-    for (int i = tid; i < HP * KX; i += NT) {          // W0p[r][s] = W0^T[r][slot_col(s)]
-      const int r = i / KX, s = i % KX;
-      W0p[i] = w0[r * INP + slot_col(s)];
-    }
-    const bf16_t* w1 = p.wq + p.off_w1;
-    for (int i = tid; i < HP * HP; i += NT) {          // W1p[R][s] = W1^T[R][pi(s)] (swizzled)
-      const int R = i >> 7, s = i & 127;
-      W1p[w1_off(R, s)] = w1[R * HP + pi_unit(s)];
-    }
-    const bf16_t* w2 = p.wq + p.off_w2;
-    for (int i = tid; i < 5 * HP; i += NT) {           // W2p[a][s] = W2^T[a][pi(s)] (rows 3, 4: padding rows)
-      const int a = i >> 7, s = i & 127;
-      W2p[i] = w2[a * HP + pi_unit(s)];
-    }
-    for (int i = tid; i < HP; i += NT) sB1[i] = p.wf[p.off_b1 + i];
-    if (tid < 16) sB2[tid] = tid < 4 ? p.wf[p.off_b2 + tid] : 0.f;
-   }
-    if (tid < 16) ctl[tid] = 0;
-    if (DYN && tid == 0) {
-      int r = 0;
-      while (r < 3 && static_chunk(r) >= 0) ++r;
-      if (r < 3) ctl[CTL_NROUNDS] = r + 1;   // the static rounds already end the run
-    }
-  }
-  __syncthreads();
-
-  if (wave < ND) {
-    // ================================================================ DATA WAVE
+  // ------------------------------------------------------------------ data waves: schedule, first-tile loads
+  // (declared ahead of the prologue: with WS_EARLY_LOADS the data waves' branch issues tile 0's loads around its
+  // share of the image DMA; unused by the gradient waves)
     const int d = wave;
-    float st_reward = 0.f, st_loss = 0.f, st_explore = 0.f, st_done = 0.f, st_fsum = 0.f, st_fsq = 0.f,
-          st_qslot = 0.f;
-    const float b2v[3] = {sB2[0], sB2[1], sB2[2]};
-
     // chunk ids of rounds k, k + 1, k + 2 (uniform); dynamic: -1 = no such round
     int ck0 = DYN ? static_chunk(0) : (int)blockIdx.x, ck1 = DYN ? static_chunk(1) : 0, ck2 = DYN ? static_chunk(2) : 0;
     // dynamic: the chunk id of round r >= 3 from the ring (data wave 0 writes it one tile ahead of use)
@@ -410,9 +388,85 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
       pe = r_[4];                                                                                \
     }                                                                                            \
   }
-    WS_LOAD_ENV(0, 0, e_pos, e_b, e_sh, e_val, e_rs, e_ep, e_sc)
-    WS_LOAD_PRICES(0, 0, e_pos)
-    WS_LOAD_ENV(1, 1, n_pos, n_b, n_sh, n_val, n_rs, n_ep, n_sc)
+  // ------------------------------------------------------------------ prologue: weight images, ring state
+  // the images as one 87,872-byte run (oW0 .. oSLOT, built by the optimizer pass): 16 bytes per lane and
+  // LDS-DMA instruction, 11 per wave, all in flight at once (the gather below takes ~10 us per launch:
+  // profiles/r5_ws_prologue.md).  Unrolled, all but the last copy unconditional: a counted vmcnt wait of the
+  // compiler's for a load issued before them then leaves the copies in flight
+#define WS_IMAGE_DMA()                                                                            \
+  {                                                                                              \
+    constexpr int NCH = (oSLOT - oW0) / 16, NIT = ((NCH + 63) / 64 + NW - 1) / NW;               \
+    _Pragma("unroll") for (int i = 0; i < NIT; ++i) {                                            \
+      const int j = wave + NW * i, c = j * 64 + lane;                                            \
+      if ((NW * i + NW) * 64 <= NCH || c < NCH)                                                  \
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p.wimg + 16 * c),        \
+                                         (__attribute__((address_space(3))) void*)(smem + oW0 + 1024 * j), 16, 0, 0); \
+    }                                                                                            \
+  }
+  // WS_EARLY_LOADS with the DMA prologue: each kind of wave issues its copies, waits for them and joins the
+  // barrier in its own branch below -- the data waves with tile 0's loads around the copies: the env state before
+  // them, the price windows (whose addresses wait for it) right behind them, so both HBM round trips run under
+  // the image copy
+  const bool early = WS_EARLY_LOADS && p.wimg != nullptr;
+#if defined(WS_PROLOGUE_REPS) && WS_PROLOGUE_REPS > 1   // timing build csrc/ab/qstep_ws_pro2.hip: images built twice
+  for (int rep_ = 0; rep_ < WS_PROLOGUE_REPS; ++rep_) {
+    __syncthreads();
+#else
+  {
+#endif
+   if (early) {
+    // (the copies are issued in the two branches below)
+   } else if (p.wimg != nullptr) {
+    WS_IMAGE_DMA()
+    __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): this wave's copies landed (the barrier below joins the waves)
+   } else {
+    const bf16_t* w0 = p.wq + p.off_w0;
+    for (int i = tid; i < HP * KX; i += NT) {          // W0p[r][s] = W0^T[r][slot_col(s)]
+      const int r = i / KX, s = i % KX;
+      W0p[i] = w0[r * INP + slot_col(s)];
+    }
+    const bf16_t* w1 = p.wq + p.off_w1;
+    for (int i = tid; i < HP * HP; i += NT) {          // W1p[R][s] = W1^T[R][pi(s)] (swizzled)
+      const int R = i >> 7, s = i & 127;
+      W1p[w1_off(R, s)] = w1[R * HP + pi_unit(s)];
+    }
+    const bf16_t* w2 = p.wq + p.off_w2;
+    for (int i = tid; i < 5 * HP; i += NT) {           // W2p[a][s] = W2^T[a][pi(s)] (rows 3, 4: padding rows)
+      const int a = i >> 7, s = i & 127;
+      W2p[i] = w2[a * HP + pi_unit(s)];
+    }
+    for (int i = tid; i < HP; i += NT) sB1[i] = p.wf[p.off_b1 + i];
+    if (tid < 16) sB2[tid] = tid < 4 ? p.wf[p.off_b2 + tid] : 0.f;
+   }
+    if (tid < 16) ctl[tid] = 0;
+    if (DYN && tid == 0) {
+      int r = 0;
+      while (r < 3 && static_chunk(r) >= 0) ++r;
+      if (r < 3) ctl[CTL_NROUNDS] = r + 1;   // the static rounds already end the run
+    }
+  }
+  if (!early) __syncthreads();
+
+  if (wave < ND) {
+    // ================================================================ DATA WAVE
+    float st_reward = 0.f, st_loss = 0.f, st_explore = 0.f, st_done = 0.f, st_fsum = 0.f, st_fsq = 0.f,
+          st_qslot = 0.f;
+    if (early) {
+      WS_LOAD_ENV(0, 0, e_pos, e_b, e_sh, e_val, e_rs, e_ep, e_sc)
+      __builtin_amdgcn_sched_barrier(0);
+      WS_IMAGE_DMA()
+      __builtin_amdgcn_sched_barrier(0);
+      WS_LOAD_PRICES(0, 0, e_pos)
+      WS_LOAD_ENV(1, 1, n_pos, n_b, n_sh, n_val, n_rs, n_ep, n_sc)
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0): the images must have landed before any wave passes the barrier
+      __syncthreads();
+    } else {
+      WS_LOAD_ENV(0, 0, e_pos, e_b, e_sh, e_val, e_rs, e_ep, e_sc)
+      WS_LOAD_PRICES(0, 0, e_pos)
+      WS_LOAD_ENV(1, 1, n_pos, n_b, n_sh, n_val, n_rs, n_ep, n_sc)
+    }
+    const float b2v[3] = {sB2[0], sB2[1], sB2[2]};
 
     unsigned long long* stamps = ((WS_STAMPS & 1) && p.stamps != nullptr && blockIdx.x == 0 && d == 0 && lane == 0)
                                      ? p.stamps : nullptr;
@@ -450,6 +504,22 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
     WS_WRITE_BACK() w_e = -1;                                                                    \
   }
 
+    // U16: the head of the features -- the window's odd-start shift, its last and next tick and their reciprocals
+    // -- from tl, the first load of the window to land, and the tile's position (e_pos).  HOIST: formed for
+    // tile k + 1 at the end of tile k (tile 0: here) and carried over the back edge
+    constexpr bool HOIST = U16 && WS_TICK_HOIST;
+    unsigned h_shb = 0u;
+    float h_lastw = 0.f, h_vneww = 0.f, h_inv = 0.f, h_invn = 0.f;
+    auto tick_head = [&]() {
+      h_shb = (unsigned)(min(max(e_pos, 0), p.T - HWIN - 1) & 1) * 2u;
+      const unsigned t01 = __builtin_amdgcn_alignbyte(tl.y, tl.x, h_shb);
+      h_lastw = (float)(t01 & 0xFFFFu);
+      h_vneww = (float)(t01 >> 16);
+      h_inv = WS_TICK_RCP ? tick_rcp(h_lastw) : __fdiv_rn(1.0f, h_lastw);
+      h_invn = WS_TICK_RCP ? tick_rcp(h_vneww) : __fdiv_rn(1.0f, h_vneww);
+    };
+    if (HOIST) tick_head();
+
     for (int k = 0; DYN ? ck0 >= 0 : k < nmy; ++k) {
       WS_STAMP(0);
       const int chunk = DYN ? ck0 : (int)blockIdx.x + k * (int)gridDim.x;
@@ -461,10 +531,10 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
       float lastw, vnew_w, last, vnew;
       unsigned shb = 0u;   // U16: 2 when the tile's window starts at an odd tick (bytes to drop)
       if (U16) {
-        shb = (unsigned)(min(max(e_pos, 0), p.T - HWIN - 1) & 1) * 2u;
-        const unsigned t01 = __builtin_amdgcn_alignbyte(tl.y, tl.x, shb);
-        lastw = (float)(t01 & 0xFFFFu);
-        vnew_w = (float)(t01 >> 16);
+        if (!HOIST) tick_head();
+        shb = h_shb;
+        lastw = h_lastw;
+        vnew_w = h_vneww;
         last = __fmul_rn(lastw, e_sc);
         vnew = __fmul_rn(vnew_w, e_sc);
       } else {
@@ -473,8 +543,8 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
       }
       float inv = 0.f, invn = 0.f;
       if (FEAT) {
-        inv = __fdiv_rn(1.0f, lastw);
-        invn = __fdiv_rn(1.0f, vnew_w);
+        inv = U16 ? h_inv : __fdiv_rn(1.0f, lastw);
+        invn = U16 ? h_invn : __fdiv_rn(1.0f, vnew_w);
       }
       auto fx = [&](float w) {
         return FEAT ? __fmaf_rn(w, inv, -1.0f) : w;
@@ -633,6 +703,9 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
       WS_PIN(qa);
       WS_SB();
       WS_STAMP(6);
+      // Q(x')'s first layer-2 W1 fragments: read here, their LDS latency runs under the env step
+      s8v A2npre[WS_L2NPRE > 0 ? WS_L2NPRE : 1];
+      layer2_pre<WS_L2NPRE>(W1p, l16, g4, A2npre);
       // ---------------------------------------------------------------- epsilon-greedy + env step (lanes g4 == 0)
       float b2 = 0.f, rew = 0.f, q0 = 0.f, q1 = 0.f, q2 = 0.f;
       int s2 = 0, act = 0;
@@ -669,7 +742,7 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) a2[i] = *reinterpret_cast<const f4v*>(sB1 + 16 * i + 4 * g4);
       WS_SB();
-      for (int rep = 0; rep < WS_L2REP; ++rep) layer2(W1p, l16, g4, H1n, a2, w2row, w2f);
+      for (int rep = 0; rep < WS_L2REP; ++rep) layer2<WS_L2NPRE>(W1p, l16, g4, H1n, a2, w2row, w2f, A2npre);
       s8v H2n[4];
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) H2n[ks] = cat8(relu_bf(a2[2 * ks]), relu_bf(a2[2 * ks + 1]));
@@ -767,6 +840,11 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
         ck0 = ck1;
         ck1 = ck2;
       }
+      if (HOIST) {   // the next tile's (its windows were requested at Q(x')'s layer 2; the wait covers tl only)
+        WS_SB();
+        tick_head();
+        WS_PIN(h_inv); WS_PIN(h_invn); WS_PIN(h_lastw);
+      }
       WS_SB();
       WS_STAMP(11);
     }
@@ -787,6 +865,11 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
     __syncthreads();
   } else {
     // ================================================================ GRADIENT WAVE
+    if (early) {
+      WS_IMAGE_DMA()
+      __builtin_amdgcn_s_waitcnt(0xF70);   // vmcnt(0)
+      __syncthreads();
+    }
     const int gw = wave - ND;
     // owns hidden units 32 gw .. 32 gw + 31 of both layers, dW2 columns likewise
     f4v gW0[2][13], gW1[2][8], gW2[2];
@@ -826,9 +909,25 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
     // 4-element fragments side by side (cat8), no data moves between lanes.  dZ1 stays per slot (K = u2);
     // its W1^T fragments are read once for both.
     int nseqv = DYN ? 0x7FFFFFF0 : nseq;   // dynamic: found when the data waves report the round count
+#if WS_GW1PRE > 0
+    // dZ1's B operands: W1p, transposed, for this wave's 32 units -- loop-invariant.  The fragments of the first
+    // WS_GW1PRE k-steps (two per k-step, 4 VGPRs each) are read ahead of the wait for the slot pair and land
+    // under it; the others ahead of their MFMAs inside the phase
+    s8v wtp[WS_GW1PRE][2];
+#endif
     for (int q = 0; q < nseqv; q += 2) {
       const int sa = q % NSLOT, sb = (q + 1) % NSLOT;
       WS_GST(0);
+#if WS_GW1PRE > 0
+#pragma unroll
+      for (int ks = 0; ks < WS_GW1PRE; ++ks)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          const int R = 32 * ks + 4 * g4 + (l16 >> 2), col = pi_pos4(2 * gw + t, qq);
+          wtp[ks][t] = cat8(lds_tr4(W1p + w1_off(R, col)), lds_tr4(W1p + w1_off(R + 16, col)));
+        }
+      WS_SB();
+#endif
       if (DYN) {
         // the slot pair of round q / ND -- or the end of the run (the round count is known by then)
         if (wait_full_or_end(p, ctl, sa, q)) {
@@ -865,7 +964,12 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int col = pi_pos4(2 * gw + t, qq);
+#if WS_GW1PRE > 0
+          const s8v wt = ks < WS_GW1PRE ? wtp[ks < WS_GW1PRE ? ks : 0][t]
+                                        : cat8(lds_tr4(W1p + w1_off(R, col)), lds_tr4(W1p + w1_off(R + 16, col)));
+#else
           const s8v wt = cat8(lds_tr4(W1p + w1_off(R, col)), lds_tr4(W1p + w1_off(R + 16, col)));
+#endif
           c1a[t] = mfma32(aza, wt, c1a[t]);
           c1b[t] = mfma32(azb, wt, c1b[t]);
         }
@@ -985,6 +1089,7 @@ __global__ void __launch_bounds__(NT, 1) qstep_ws_kernel(QStepParams p) {
 #undef WS_SB
 #undef WS_PIN
 #undef WS_GST
+#undef WS_IMAGE_DMA
   // ------------------------------------------------------------------ workgroup statistics (data waves' sums)
   if (tid < NSTAT) {
     float t = 0.f;

@@ -198,6 +198,9 @@ def _bind_optional(L: C.CDLL) -> None:
     if hasattr(L, "st_occupy"):   # csrc/diag.hip
         L.st_occupy.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.st_occupy.restype = C.c_int
+    if hasattr(L, "st_tick_rcp_table"):   # csrc/diag.hip
+        L.st_tick_rcp_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.st_tick_rcp_table.restype = C.c_int
     if hasattr(L, "st_mlp_fwd_f32"):
         L.st_mlp_fwd_f32.restype = C.c_int
         L.st_td_update_f32.restype = C.c_int
@@ -302,6 +305,15 @@ def tick16(bank: torch.Tensor, quantize: bool):
     if not quantize and int(bad.item()) != 0:
         return None
     return ticks, scale
+
+
+def tick_rcp_table(device) -> tuple:
+    """For every tick x = 1 .. 65,535 the bits (int32) of the IEEE division 1 / x and of the ws step kernel's tick
+    reciprocal (csrc/qstep.h ``tick_rcp``), as computed on the device (csrc/diag.hip)."""
+    div = torch.zeros(65535, dtype=torch.int32, device=device)
+    rcp = torch.ones(65535, dtype=torch.int32, device=device)
+    check(lib().st_tick_rcp_table(ptr(div), ptr(rcp), stream_handle()), "st_tick_rcp_table")
+    return div, rcp
 
 
 def tick16_quantize_(bank: torch.Tensor) -> torch.Tensor:
