@@ -21,8 +21,12 @@
 //     exactly one wave's unit range, so amax is a 4-lane reduction;
 //   * Q = W_q h is reduced across waves through LDS; wave 0 runs epsilon-greedy
 //     (Philox), the minute-bar trading env, and writes the replay segment.
+// The bar itself (weight prologue: gru_weights.h; net on one 16-env tile: gru_net_tile.h; Q row: gru_common.h) is
+// defined once for both actors here, the backtest (gru_rollout.hip) and the server (gru_serve.hip); the trading
+// rule is minute_rule.h's, and the actors' env step (act_step) is one function for both.
 // Learner: csrc/gru_learn.hip.
 #include "gru_common.h"
+#include "minute_rule.h"
 
 namespace st {
 
@@ -221,25 +225,136 @@ struct ActLds {
 };
 static_assert(ActLds::BYTES <= 160 * 1024, "actor LDS");
 
-// build the x row (bf16 [RF]) from bar features mf / close c into LDS and (if rx_row) the replay segment
-ST_DEV void build_x(const GruAct& p, uint4 mf, float c, int t, int es, int pz, float entry, bf16_t* sx_row,
-                    bf16_t* rx_row) {
-  const float upnl = pz ? (c / entry - 1.f) * 100.f : 0.f;
-  uint4 w1;
-  w1.x = pack_bf2((float)pz, upnl);
-  w1.y = pack_bf2((float)(t - es) * p.inv_ep_len, 1.f);
-  w1.z = 0u;
-  w1.w = 0u;
-  const uint4 z = {0u, 0u, 0u, 0u};
-  uint4* d = reinterpret_cast<uint4*>(sx_row);
-  d[0] = mf; d[1] = w1; d[2] = z; d[3] = z;
-  if (rx_row) {
-    uint4* r = reinterpret_cast<uint4*>(rx_row);
-    r[0] = mf; r[1] = w1; r[2] = z; r[3] = z;
-  }
-}
+// ---------------------------------------------------------------- what the two actor kernels share
+// (the bar itself -- weights, net, Q row -- is gru_common.h's; the trading rule is minute_rule.h's)
+
+// wave 0's state of one env between env phases: the env's scalars, bars t (cA, rA) and t + 1 (cB, rB, fB:
+// prefetched one env phase ahead) and its replay slot
+struct ActEnv {
+  int t, es, pz, eps;
+  float en, er, lr, cA, cB, rA, rB;
+  uint4 fB;
+  unsigned slot;
+};
+
 ST_DEV uint4 bar_feat(const GruAct& p, int e, int t) {
   return *reinterpret_cast<const uint4*>(p.feat + ((size_t)e * p.T + t) * RMF);
+}
+
+// the x row (bf16 [RF]) of env state v at a bar with features mf / close c, into LDS and (if rx_row) the replay
+// segment
+ST_DEV void build_x(const GruAct& p, uint4 mf, float c, const ActEnv& v, bf16_t* sx_row, bf16_t* rx_row) {
+  const uint4 w1 = minute_x_env(v.pz, v.en, c, v.t - v.es, p.inv_ep_len);
+  minute_x_row(sx_row, mf, w1);
+  if (rx_row) minute_x_row(rx_row, mf, w1);
+}
+
+// h of the chunk at e0 into registers (accumulator layout); with_h0: also into the replay segments as bf16
+ST_DEV void load_h(const GruAct& p, float (&hr)[2][2][4], int e0, unsigned long long seg0, bool with_h0, int wave,
+                   int l16, int g4) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      const int e = e0 + 16 * n + l16, u0 = 32 * wave + 16 * m + 4 * g4;
+      const float4 v = *reinterpret_cast<const float4*>(p.h + (size_t)e * RH + u0);
+      hr[m][n][0] = v.x; hr[m][n][1] = v.y; hr[m][n][2] = v.z; hr[m][n][3] = v.w;
+      if (with_h0) {
+        const size_t slot = (size_t)((seg0 + (unsigned long long)e) % (unsigned long long)p.cap);
+        lds_st4(p.rh0 + slot * RH + u0, v.x, v.y, v.z, v.w);   // 8-byte global store of h0 (bf16)
+      }
+    }
+}
+
+// the chunk's Philox draws for all S steps, by every thread (off the env phase's serial path): per (step, env)
+// the explore coin, the random action, the restart draw and the global step
+ST_DEV void stage_draws(const GruAct& p, f4v* sU, int e0, unsigned long long launch, int tid) {
+  for (int i = tid; i < p.S * RN; i += RT) {
+    const int ss = i / RN, e = e0 + (i % RN);
+    const unsigned long long step = launch * (unsigned long long)p.S + (unsigned long long)ss;
+    uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(step & 0xFFFFFFFFull), c2 = (uint32_t)(step >> 32),
+             c3 = 0x47525531u;
+    philox4x32(c0, c1, c2, c3, p.key0, p.key1);
+    f4v u;
+    u[0] = u24(c0); u[1] = u24(c1); u[2] = u24(c2); u[3] = (float)step;
+    sU[i] = u;
+  }
+}
+
+// env `me` as the last launch left it, with bars t and t + 1
+ST_DEV ActEnv load_env(const GruAct& p, int me, unsigned long long seg0) {
+  ActEnv v;
+  v.t = p.pos[me]; v.es = p.ep_start[me]; v.pz = p.position[me]; v.en = p.entry[me];
+  v.er = p.ep_ret[me]; v.eps = p.episodes[me]; v.lr = p.last_ret[me];
+  v.slot = (unsigned)((seg0 + (unsigned long long)me) % (unsigned long long)p.cap);
+  const size_t o = (size_t)me * p.T + v.t;
+  v.cA = p.close[o];
+  v.cB = p.close[o + 1];
+  v.rA = p.ret[o];
+  v.rB = p.ret[o + 1];
+  v.fB = bar_feat(p, me, v.t + 1);
+  return v;
+}
+ST_DEV void store_env(const GruAct& p, int me, const ActEnv& v) {
+  p.pos[me] = v.t; p.ep_start[me] = v.es; p.position[me] = v.pz; p.entry[me] = v.en;
+  p.ep_ret[me] = v.er; p.episodes[me] = v.eps; p.last_ret[me] = v.lr;
+}
+
+struct ActStep {
+  int a;          // the action taken
+  float rew;
+  float fin;      // the episode's return if it ended at this bar, else 0
+  bool exploit, done;
+};
+
+// one env step: epsilon-greedy action from the Q row and the draw row u (explore coin, random action, restart
+// draw, global step) under the ramped epsilon, the move at bar t, the episode bookkeeping; on an episode's end
+// the env restarts flat at the bar drawn by u[2].  v.t is then the next bar (its data: act_next_bar)
+ST_DEV ActStep act_step(const GruAct& p, ActEnv& v, const float (&q)[3], const f4v& u) {
+  ActStep r;
+  const int greedy = first_max3(q[0], q[1], q[2]);
+  r.exploit = u[0] < fminf(p.eps, u[3] * p.inv_ramp);
+  const int rnd = min((int)(u[1] * 3.0f), 2);
+  r.a = r.exploit ? greedy : rnd;
+  const MinuteMove mv = minute_move(r.a, v.pz, v.en, v.cA, v.rA, p.cost);
+  v.en = mv.entry;
+  r.rew = mv.reward;
+  v.er += r.rew;
+  int t1 = v.t + 1;
+  r.done = (t1 - v.es) >= p.ep_len;
+  r.fin = 0.f;
+  if (r.done) {
+    v.eps += 1;
+    v.lr = v.er;
+    r.fin = v.er;
+    v.es = min((int)(u[2] * (float)(p.T - p.ep_len - 1)), p.T - p.ep_len - 2);
+    t1 = v.es;
+    v.pz = 0;
+    v.er = 0.f;
+  } else {
+    v.pz = mv.position;
+  }
+  v.t = t1;
+  return r;
+}
+
+// features / close / return of the bar the env moved to: the prefetched bar unless the episode restarted (rare:
+// loaded now, when any lane of the wave restarted)
+ST_DEV void act_next_bar(const GruAct& p, const ActEnv& v, int me, bool done, uint4& fx, float& cx, float& rx) {
+  fx = v.fB;
+  cx = v.cB;
+  rx = v.rB;
+  if (__builtin_amdgcn_ballot_w64(done) != 0ull) {
+    const size_t o = (size_t)me * p.T + v.t;
+    const uint4 fr = bar_feat(p, me, v.t);
+    const float cr = p.close[o], rr = p.ret[o];
+    fx.x = done ? fr.x : fx.x;   // per component: a uint4 ternary lowers to a stack select
+    fx.y = done ? fr.y : fx.y;
+    fx.z = done ? fr.z : fx.z;
+    fx.w = done ? fr.w : fx.w;
+    cx = done ? cr : cx;
+    rx = done ? rr : rx;
+  }
 }
 
 __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
@@ -256,37 +371,7 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
 
   const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int i = tid; i < RW * 6 * 64; i += RT) reinterpret_cast<s8v*>(lds + ActLds::WX)[i] = p.wih[i];
-  for (int i = tid; i < 4 * RH; i += RT) {
-    sB[i] = p.bias4[i];
-    sWq[i] = p.wq[i];
-  }
-  // resident MX-fp8 W_hh fragments of this wave's 32 units x 3 gates (96 VGPRs + 12 scales)
-  i8v Wh[3][2][2];
-  int Ws4[3] = {0, 0, 0};   // 12 E8M0 scales packed 4 per VGPR: (g, m, ks) -> reg g, byte 2m + ks
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int idx = (((wave * 3 + g) * 2 + m) * 2 + ks) * 64 + lane;
-        Wh[g][m][ks] = p.whh8[idx];
-        Ws4[g] |= (p.whhs[idx] & 0xFF) << (8 * (2 * m + ks));
-      }
-  const s8v* myWx = sWx + wave * 6 * 64 + lane;
-  // Q head as one bf16 MFMA per env tile: A = W_q rows (a < 3, zero-padded to 16) over this
-  // wave's 32 units, K ordered like the GRU accumulators the B operand is built from:
-  // element j of lane group q <-> unit 32w + (j < 4 ? 4q + j : 16 + 4q + j - 4)
-  s8v WqA;
-  {
-    const int a = l16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int u = 32 * wave + (j < 4 ? 4 * g4 + j : 16 + 4 * g4 + j - 4);
-      WqA[j] = (short)f2bf(a < 3 ? p.wq[a * RH + u] : 0.f);
-    }
-  }
+#include "gru_weights.h"
   const unsigned long long launch = p.ctrl[0];
   const unsigned long long seg0 = p.rctrl[0];
   const int nchunks = p.E / RN, S = p.S;
@@ -295,52 +380,20 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
   for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
     const int e0 = chunk * RN;
     float hr[2][2][4];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        const int e = e0 + 16 * n + l16, u0 = 32 * wave + 16 * m + 4 * g4;
-        const float4 v = *reinterpret_cast<const float4*>(p.h + (size_t)e * RH + u0);
-        hr[m][n][0] = v.x; hr[m][n][1] = v.y; hr[m][n][2] = v.z; hr[m][n][3] = v.w;
-        const size_t slot = (size_t)((seg0 + (unsigned long long)e) % (unsigned long long)p.cap);
-        lds_st4(p.rh0 + slot * RH + u0, v.x, v.y, v.z, v.w);   // 8-byte global store of h0 (bf16)
-      }
+    load_h(p, hr, e0, seg0, true, wave, l16, g4);
     quant_h(hr, sH8, sSc, wave, l16, g4);
     // env state lives in wave 0: lane l and l + 32 both carry env e0 + (l & 31) (the upper half
     // mirrors the lower one so every load is unconditional; only lanes < RN store)
-    int t_ = 0, es_ = 0, pz_ = 0, eps_ = 0;
-    float en_ = 0.f, er_ = 0.f, lr_ = 0.f;
-    float cA = 0.f, cB = 0.f;      // close[t], close[t+1] (prefetched one env phase ahead)
-    float rA = 0.f, rB = 0.f;      // ret[t], ret[t+1]
-    uint4 fB = {0u, 0u, 0u, 0u};   // features of bar t+1
+    ActEnv v = {};
     float st_rew = 0.f, st_exp = 0.f, st_fin = 0.f, st_dn = 0.f;
-    size_t slot_ = 0;
     const int me = e0 + (lane & (RN - 1));
     const bool writer = lane < RN;
     if (wave == 0) {
-      t_ = p.pos[me]; es_ = p.ep_start[me]; pz_ = p.position[me]; en_ = p.entry[me]; er_ = p.ep_ret[me];
-      eps_ = p.episodes[me]; lr_ = p.last_ret[me];
-      slot_ = (size_t)((seg0 + (unsigned long long)me) % (unsigned long long)p.cap);
-      const size_t o = (size_t)me * p.T + t_;
-      cA = p.close[o];
-      cB = p.close[o + 1];
-      rA = p.ret[o];
-      rB = p.ret[o + 1];
-      fB = bar_feat(p, me, t_ + 1);
-      const uint4 f0 = bar_feat(p, me, t_);
-      if (writer) build_x(p, f0, cA, t_, es_, pz_, en_, sX + lane * XS, p.rx + slot_ * (size_t)(S + 1) * RF);
+      v = load_env(p, me, seg0);
+      const uint4 f0 = bar_feat(p, me, v.t);
+      if (writer) build_x(p, f0, v.cA, v, sX + lane * XS, p.rx + (size_t)v.slot * (size_t)(S + 1) * RF);
     }
-    // the chunk's Philox draws for all S steps, by every thread (off the env phase's serial path)
-    for (int i = tid; i < S * RN; i += RT) {
-      const int ss = i / RN, e = e0 + (i % RN);
-      const unsigned long long step = launch * (unsigned long long)S + (unsigned long long)ss;
-      uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(step & 0xFFFFFFFFull), c2 = (uint32_t)(step >> 32),
-               c3 = 0x47525531u;
-      philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-      f4v u;
-      u[0] = u24(c0); u[1] = u24(c1); u[2] = u24(c2); u[3] = (float)step;
-      sU[i] = u;
-    }
+    stage_draws(p, sU, e0, launch, tid);
     __syncthreads();
 
     for (int s = 0; s < S; ++s) {
@@ -355,72 +408,16 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
       const bf16_t* cX = sX + cur * RN * XS;
       const unsigned char* cH = sH8 + cur * RN * HS;
       const int* cS = sSc + cur * RN * SCS;
-      // one 16-env tile at a time keeps the accumulators at 32 VGPRs (W_hh holds 108)
+      // (a lambda, not bare statements: with the stamp's branch in the loop body the bare form spills 36 B a
+      // lane, this one the 28 B the kernel always had; profiles/gru_shared_bar.md)
+      auto net_tile = [&](int n) __attribute__((always_inline)) {
+        float (&hrt)[2][2][4] = hr;
+#define GRU_TILE_STAMP if (n == 0) { GR_STAMP(1) }
+#include "gru_net_tile.h"
+#undef GRU_TILE_STAMP
+      };
 #pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        f4v ar[2], az[2], anx[2], anh[2];   // accumulators start at the biases (b_ir+b_hr, b_iz+b_hz, b_in, b_hn)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const int u0 = 32 * wave + 16 * m + 4 * g4;
-          ar[m] = *reinterpret_cast<const f4v*>(sB + u0);
-          az[m] = *reinterpret_cast<const f4v*>(sB + RH + u0);
-          anx[m] = *reinterpret_cast<const f4v*>(sB + 2 * RH + u0);
-          anh[m] = *reinterpret_cast<const f4v*>(sB + 3 * RH + u0);
-        }
-        const int row = 16 * n + l16;
-        // x part: bf16 16x16x32 (W_ih fragments from LDS)
-        {
-          const s8v xb = lds_ld8(cX + row * XS + 8 * g4);
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            ar[m] = mfma32(myWx[(0 * 2 + m) * 64], xb, ar[m]);
-            az[m] = mfma32(myWx[(1 * 2 + m) * 64], xb, az[m]);
-            anx[m] = mfma32(myWx[(2 * 2 + m) * 64], xb, anx[m]);
-          }
-        }
-        // h part: MX-fp8 16x16x128, two K steps over the 256 hidden units
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          // bytes 0..15: units 128ks + 16g4 + [0,16); bytes 16..31: units 128ks + 64 + 16g4 + [0,16)
-          const uint4 h0 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 16 * g4);
-          const uint4 h1 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 64 + 16 * g4);
-          i8v hb;
-          hb[0] = (int)h0.x; hb[1] = (int)h0.y; hb[2] = (int)h0.z; hb[3] = (int)h0.w;
-          hb[4] = (int)h1.x; hb[5] = (int)h1.y; hb[6] = (int)h1.z; hb[7] = (int)h1.w;
-          const int sc = cS[row * SCS + 4 * ks + g4];   // scale of K-block g4 = units of wave 4ks + g4
-#define ST_MX3(M, KS)                                                              \
-  ar[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[0][M][KS], hb, ar[M], Ws4[0], sc);          \
-  az[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[1][M][KS], hb, az[M], Ws4[1], sc);          \
-  anh[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[2][M][KS], hb, anh[M], Ws4[2], sc);
-          if (ks == 0) { ST_MX3(0, 0) ST_MX3(1, 0) } else { ST_MX3(0, 1) ST_MX3(1, 1) }
-#undef ST_MX3
-        }
-        if (n == 0) { GR_STAMP(1) }
-        // GRU update in registers (lane: units u0..u0+3 of tile m, env 16n + l16)
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float r = sigm_ps(ar[m][i]);
-            const float z = sigm_ps(az[m][i]);
-            const float nn = tanh_ps(__builtin_fmaf(r, anh[m][i], anx[m][i]));
-            hr[m][n][i] = __builtin_fmaf(z, hr[m][n][i] - nn, nn);
-          }
-        // Q partials of this wave's units: one MFMA, h (bf16) taken straight from the accumulator layout
-        {
-          s8v hb;
-          const uint32_t p0 = pack_bf2(hr[0][n][0], hr[0][n][1]), p1 = pack_bf2(hr[0][n][2], hr[0][n][3]);
-          const uint32_t p2 = pack_bf2(hr[1][n][0], hr[1][n][1]), p3 = pack_bf2(hr[1][n][2], hr[1][n][3]);
-          hb[0] = (short)(p0 & 0xFFFF); hb[1] = (short)(p0 >> 16); hb[2] = (short)(p1 & 0xFFFF); hb[3] = (short)(p1 >> 16);
-          hb[4] = (short)(p2 & 0xFFFF); hb[5] = (short)(p2 >> 16); hb[6] = (short)(p3 & 0xFFFF); hb[7] = (short)(p3 >> 16);
-          const f4v qp = mfma32(WqA, hb, zero4());
-          if (g4 == 0) {   // rows a = 0..2 of the 16x16 result live in lanes 0..15, registers 0..2
-            sQp[(wave * 3 + 0) * RN + row] = qp[0];
-            sQp[(wave * 3 + 1) * RN + row] = qp[1];
-            sQp[(wave * 3 + 2) * RN + row] = qp[2];
-          }
-        }
-      }
+      for (int n = 0; n < 2; ++n) net_tile(n);
       GR_STAMP(2)
       quant_h(hr, sH8 + nxt * RN * HS, sSc + nxt * RN * SCS, wave, l16, g4);
       GR_STAMP(3)
@@ -431,63 +428,19 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
       // ---------------------------------------------------------- env step (wave 0)
       if (wave == 0) {
         float q[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          float v = sWq[3 * RH + a];
-#pragma unroll
-          for (int w = 0; w < RW; ++w) v += sQp[(w * 3 + a) * RN + (lane & (RN - 1))];
-          q[a] = v;
-        }
-        int greedy = 0;
-        const float qg = q[1] > q[0] ? q[1] : q[0];   // select chain: no stack-indexed q[greedy]
-        if (q[1] > q[0]) greedy = 1;
-        if (q[2] > qg) greedy = 2;
-        const f4v u = sU[s * RN + (lane & (RN - 1))];   // (explore coin, random action, reset, step)
-        const bool exploit = u[0] < fminf(p.eps, u[3] * p.inv_ramp);
-        const int rnd = min((int)(u[1] * 3.0f), 2);
-        const int a = exploit ? greedy : rnd;
-        const int np = a == 0 ? 1 : (a == 1 ? 0 : pz_);
-        const bool trade = np != pz_;
-        if (trade && np == 1) en_ = cA;
-        const float rew = (float)np * rA - (trade ? p.cost : 0.f);
-        er_ += rew;
-        int t1 = t_ + 1;
-        const bool done = (t1 - es_) >= p.ep_len;
-        float fin = 0.f;
-        if (done) {
-          eps_ += 1;
-          lr_ = er_;
-          fin = er_;
-          es_ = min((int)(u[2] * (float)(p.T - p.ep_len - 1)), p.T - p.ep_len - 2);
-          t1 = es_;
-          pz_ = 0;
-          er_ = 0.f;
-        } else {
-          pz_ = np;
-        }
-        t_ = t1;
-        // bar t1's features: prefetched unless the episode restarted (rare: load now)
-        uint4 fx = fB;
-        float cx = cB, rx = rB;
-        if (__builtin_amdgcn_ballot_w64(done) != 0ull) {
-          const size_t o = (size_t)me * p.T + t_;
-          const uint4 fr = bar_feat(p, me, t_);
-          const float cr = p.close[o], rr = p.ret[o];
-          fx.x = done ? fr.x : fx.x;   // per component: a uint4 ternary lowers to a stack select
-      fx.y = done ? fr.y : fx.y;
-      fx.z = done ? fr.z : fx.z;
-      fx.w = done ? fr.w : fx.w;
-          cx = done ? cr : cx;
-          rx = done ? rr : rx;
-        }
+        gru_q_row(sWq, sQp, lane & (RN - 1), q);
+        const ActStep st = act_step(p, v, q, sU[s * RN + (lane & (RN - 1))]);
+        uint4 fx;
+        float cx, rx;
+        act_next_bar(p, v, me, st.done, fx, cx, rx);
         if (writer) {
-          p.ra[slot_ * S + s] = (unsigned char)a;
-          p.rr[slot_ * S + s] = rew;
-          p.rd[slot_ * S + s] = done ? 1 : 0;
-          build_x(p, fx, cx, t_, es_, pz_, en_, sX + nxt * RN * XS + lane * XS,
-                  p.rx + (slot_ * (size_t)(S + 1) + (size_t)(s + 1)) * RF);
-          sDone[lane] = done ? 1 : 0;
-          if (done) {   // the next step starts from h = 0
+          const size_t sl_ = v.slot;
+          p.ra[sl_ * S + s] = (unsigned char)st.a;
+          p.rr[sl_ * S + s] = st.rew;
+          p.rd[sl_ * S + s] = st.done ? 1 : 0;
+          build_x(p, fx, cx, v, sX + nxt * RN * XS + lane * XS, p.rx + (sl_ * (size_t)(S + 1) + (size_t)(s + 1)) * RF);
+          sDone[lane] = st.done ? 1 : 0;
+          if (st.done) {   // the next step starts from h = 0
             uint4* hz = reinterpret_cast<uint4*>(sH8 + nxt * RN * HS + lane * HS);
             const uint4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -495,20 +448,20 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
           }
           if (p.q_out && s == S - 1) {
             float* qo = p.q_out + (size_t)me * 4;
-            qo[0] = q[0]; qo[1] = q[1]; qo[2] = q[2]; qo[3] = (float)a;
+            qo[0] = q[0]; qo[1] = q[1]; qo[2] = q[2]; qo[3] = (float)st.a;
           }
-          st_rew += rew;
-          st_exp += exploit ? 0.f : 1.f;
-          st_fin += fin;
-          st_dn += done ? 1.f : 0.f;
+          st_rew += st.rew;
+          st_exp += st.exploit ? 0.f : 1.f;
+          st_fin += st.fin;
+          st_dn += st.done ? 1.f : 0.f;
         }
-        // prefetch bar t1+1 for the next env phase (issued last: a whole MFMA phase to land)
-        cA = cx;
-        rA = rx;
-        const size_t o1 = (size_t)me * p.T + min(t_ + 1, p.T - 1);
-        cB = p.close[o1];
-        rB = p.ret[o1];
-        fB = *reinterpret_cast<const uint4*>(p.feat + o1 * RMF);
+        // prefetch bar t + 1 for the next env phase (issued last: a whole MFMA phase to land)
+        v.cA = cx;
+        v.rA = rx;
+        const size_t o1 = (size_t)me * p.T + min(v.t + 1, p.T - 1);
+        v.cB = p.close[o1];
+        v.rB = p.ret[o1];
+        v.fB = *reinterpret_cast<const uint4*>(p.feat + o1 * RMF);
       }
       GR_STAMP(5)
       __syncthreads();
@@ -543,10 +496,7 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
         atomicAdd(p.stats + 3, st_fin);
       }
     }
-    if (wave == 0 && writer) {
-      p.pos[me] = t_; p.ep_start[me] = es_; p.position[me] = pz_; p.entry[me] = en_; p.ep_ret[me] = er_;
-      p.episodes[me] = eps_; p.last_ret[me] = lr_;
-    }
+    if (wave == 0 && writer) store_env(p, me, v);
     __syncthreads();
   }
 }
@@ -558,8 +508,8 @@ __global__ void __launch_bounds__(RT, 1) gru_act_kernel(GruAct p) {
 // alternates: wave 0 runs slot A's env phase of step s while every wave runs slot B's MFMA phase of
 // step s, then slot B's env phase beside slot A's MFMA phase of step s+1 -- each barrier interval
 // pairs one chunk's serial env work with the other chunk's matrix work.  Per chunk the arithmetic
-// and its order are those of gru_act_kernel (bit-identical env / replay / h), so the same tests
-// hold.  LDS: the shared weights + two slot images (S <= 32 Philox rows each) = 146 KB.
+// and its order are those of gru_act_kernel -- the same source (bit-identical env / replay / h),
+// so the same tests hold.  LDS: the shared weights + two slot images (S <= 32 Philox rows each) = 146 KB.
 constexpr int PAIR_SMAX = 32;
 struct Act2Lds {
   static constexpr int WX = 0;                                   // RW*6*64 s8v
@@ -580,13 +530,6 @@ struct Act2Lds {
 static_assert(Act2Lds::BYTES <= 160 * 1024, "two-chunk actor LDS");
 static_assert(Act2Lds::SLOT0 % 16 == 0 && Act2Lds::SLOT % 16 == 0, "16-byte aligned slots");
 
-struct ActEnv {
-  int t, es, pz, eps;
-  float en, er, lr, cA, cB, rA, rB;
-  uint4 fB;
-  unsigned slot;
-};
-
 template <int V>
 struct ActSlot {
   static constexpr int v = V;
@@ -600,33 +543,7 @@ __global__ void __launch_bounds__(RT, 1) gru_act_pair_kernel(GruAct p) {
 
   const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int i = tid; i < RW * 6 * 64; i += RT) reinterpret_cast<s8v*>(lds + Act2Lds::WX)[i] = p.wih[i];
-  for (int i = tid; i < 4 * RH; i += RT) {
-    sB[i] = p.bias4[i];
-    sWq[i] = p.wq[i];
-  }
-  i8v Wh[3][2][2];
-  int Ws4[3] = {0, 0, 0};
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int idx = (((wave * 3 + g) * 2 + m) * 2 + ks) * 64 + lane;
-        Wh[g][m][ks] = p.whh8[idx];
-        Ws4[g] |= (p.whhs[idx] & 0xFF) << (8 * (2 * m + ks));
-      }
-  const s8v* myWx = sWx + wave * 6 * 64 + lane;
-  s8v WqA;
-  {
-    const int a = l16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int u = 32 * wave + (j < 4 ? 4 * g4 + j : 16 + 4 * g4 + j - 4);
-      WqA[j] = (short)f2bf(a < 3 ? p.wq[a * RH + u] : 0.f);
-    }
-  }
+#include "gru_weights.h"
   const unsigned long long launch = p.ctrl[0];
   const unsigned long long seg0 = p.rctrl[0];
   const int nchunks = p.E / RN, S = p.S;
@@ -682,48 +599,18 @@ __global__ void __launch_bounds__(RT, 1) gru_act_pair_kernel(GruAct p) {
     const int cc = valid ? chunk : nchunks - 1;   // an empty slot computes on a clamped chunk, writes nothing
     const int e0 = cc * RN;
     valid_[K] = valid;
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        const int e = e0 + 16 * n + l16, u0 = 32 * wave + 16 * m + 4 * g4;
-        const float4 v = *reinterpret_cast<const float4*>(p.h + (size_t)e * RH + u0);
-        hr[K][m][n][0] = v.x; hr[K][m][n][1] = v.y; hr[K][m][n][2] = v.z; hr[K][m][n][3] = v.w;
-        if (valid) {
-          const size_t slot = (size_t)((seg0 + (unsigned long long)e) % (unsigned long long)p.cap);
-          lds_st4(p.rh0 + slot * RH + u0, v.x, v.y, v.z, v.w);
-        }
-      }
+    load_h(p, hr[K], e0, seg0, valid, wave, l16, g4);
     quant_h(hr[K], sb + Act2Lds::H8, reinterpret_cast<int*>(sb + Act2Lds::SC), wave, l16, g4);
     e0_[K] = e0;
     if (wave == 0) {
       const int me = e0 + (lane & (RN - 1));
-      ActEnv v;
-      v.t = p.pos[me]; v.es = p.ep_start[me]; v.pz = p.position[me]; v.en = p.entry[me];
-      v.er = p.ep_ret[me]; v.eps = p.episodes[me]; v.lr = p.last_ret[me];
-      v.slot = (unsigned)((seg0 + (unsigned long long)me) % (unsigned long long)p.cap);
-      const size_t o = (size_t)me * p.T + v.t;
-      v.cA = p.close[o];
-      v.cB = p.close[o + 1];
-      v.rA = p.ret[o];
-      v.rB = p.ret[o + 1];
-      v.fB = bar_feat(p, me, v.t + 1);
+      const ActEnv v = load_env(p, me, seg0);
       const uint4 f0 = bar_feat(p, me, v.t);
       if (writer)
-        build_x(p, f0, v.cA, v.t, v.es, v.pz, v.en, sX + lane * XS,
-                valid ? p.rx + (size_t)v.slot * (size_t)(S + 1) * RF : nullptr);
+        build_x(p, f0, v.cA, v, sX + lane * XS, valid ? p.rx + (size_t)v.slot * (size_t)(S + 1) * RF : nullptr);
       env_st(sl, v);
     }
-    for (int i = tid; i < S * RN; i += RT) {
-      const int ss = i / RN, e = e0 + (i % RN);
-      const unsigned long long step = launch * (unsigned long long)S + (unsigned long long)ss;
-      uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(step & 0xFFFFFFFFull), c2 = (uint32_t)(step >> 32),
-               c3 = 0x47525531u;
-      philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-      f4v u;
-      u[0] = u24(c0); u[1] = u24(c1); u[2] = u24(c2); u[3] = (float)step;
-      sU[i] = u;
-    }
+    stage_draws(p, sU, e0, launch, tid);
   };
 
   // MFMA phase of one step of a slot: gates from x (bf16) and h (MX-fp8), GRU update in registers,
@@ -737,62 +624,10 @@ __global__ void __launch_bounds__(RT, 1) gru_act_pair_kernel(GruAct p) {
     float* sQp = reinterpret_cast<float*>(sb + Act2Lds::QP);
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      f4v ar[2], az[2], anx[2], anh[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int u0 = 32 * wave + 16 * m + 4 * g4;
-        ar[m] = *reinterpret_cast<const f4v*>(sB + u0);
-        az[m] = *reinterpret_cast<const f4v*>(sB + RH + u0);
-        anx[m] = *reinterpret_cast<const f4v*>(sB + 2 * RH + u0);
-        anh[m] = *reinterpret_cast<const f4v*>(sB + 3 * RH + u0);
-      }
-      const int row = 16 * n + l16;
-      {
-        const s8v xb = lds_ld8(cX + row * XS + 8 * g4);
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          ar[m] = mfma32(myWx[(0 * 2 + m) * 64], xb, ar[m]);
-          az[m] = mfma32(myWx[(1 * 2 + m) * 64], xb, az[m]);
-          anx[m] = mfma32(myWx[(2 * 2 + m) * 64], xb, anx[m]);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const uint4 h0 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 16 * g4);
-        const uint4 h1 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 64 + 16 * g4);
-        i8v hb;
-        hb[0] = (int)h0.x; hb[1] = (int)h0.y; hb[2] = (int)h0.z; hb[3] = (int)h0.w;
-        hb[4] = (int)h1.x; hb[5] = (int)h1.y; hb[6] = (int)h1.z; hb[7] = (int)h1.w;
-        const int sc = cS[row * SCS + 4 * ks + g4];
-#define ST_MX3P(M, KS)                                                             \
-  ar[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[0][M][KS], hb, ar[M], Ws4[0], sc);          \
-  az[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[1][M][KS], hb, az[M], Ws4[1], sc);          \
-  anh[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[2][M][KS], hb, anh[M], Ws4[2], sc);
-        if (ks == 0) { ST_MX3P(0, 0) ST_MX3P(1, 0) } else { ST_MX3P(0, 1) ST_MX3P(1, 1) }
-#undef ST_MX3P
-      }
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float r = sigm_ps(ar[m][i]);
-          const float z = sigm_ps(az[m][i]);
-          const float nn = tanh_ps(__builtin_fmaf(r, anh[m][i], anx[m][i]));
-          hr[K][m][n][i] = __builtin_fmaf(z, hr[K][m][n][i] - nn, nn);
-        }
-      {
-        s8v hb;
-        const uint32_t p0 = pack_bf2(hr[K][0][n][0], hr[K][0][n][1]), p1 = pack_bf2(hr[K][0][n][2], hr[K][0][n][3]);
-        const uint32_t p2 = pack_bf2(hr[K][1][n][0], hr[K][1][n][1]), p3 = pack_bf2(hr[K][1][n][2], hr[K][1][n][3]);
-        hb[0] = (short)(p0 & 0xFFFF); hb[1] = (short)(p0 >> 16); hb[2] = (short)(p1 & 0xFFFF); hb[3] = (short)(p1 >> 16);
-        hb[4] = (short)(p2 & 0xFFFF); hb[5] = (short)(p2 >> 16); hb[6] = (short)(p3 & 0xFFFF); hb[7] = (short)(p3 >> 16);
-        const f4v qp = mfma32(WqA, hb, zero4());
-        if (g4 == 0) {
-          sQp[(wave * 3 + 0) * RN + row] = qp[0];
-          sQp[(wave * 3 + 1) * RN + row] = qp[1];
-          sQp[(wave * 3 + 2) * RN + row] = qp[2];
-        }
-      }
+      float (&hrt)[2][2][4] = hr[K];
+#define GRU_TILE_STAMP
+#include "gru_net_tile.h"
+#undef GRU_TILE_STAMP
     }
     quant_h(hr[K], sb + Act2Lds::H8 + (cur ^ 1) * RN * HS, reinterpret_cast<int*>(sb + Act2Lds::SC) + (cur ^ 1) * RN * SCS,
             wave, l16, g4);
@@ -813,66 +648,22 @@ __global__ void __launch_bounds__(RT, 1) gru_act_pair_kernel(GruAct p) {
     __builtin_amdgcn_s_waitcnt(0xF70);
     ActEnv v = env_ld(sl);
     float q[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      float v = sWq[3 * RH + a];
-#pragma unroll
-      for (int w = 0; w < RW; ++w) v += sQp[(w * 3 + a) * RN + (lane & (RN - 1))];
-      q[a] = v;
-    }
-    int greedy = 0;
-    const float qg = q[1] > q[0] ? q[1] : q[0];
-    if (q[1] > q[0]) greedy = 1;
-    if (q[2] > qg) greedy = 2;
-    const f4v u = sU[s * RN + (lane & (RN - 1))];
-    const bool exploit = u[0] < fminf(p.eps, u[3] * p.inv_ramp);
-    const int rnd = min((int)(u[1] * 3.0f), 2);
-    const int a = exploit ? greedy : rnd;
-    const int np = a == 0 ? 1 : (a == 1 ? 0 : v.pz);
-    const bool trade = np != v.pz;
-    if (trade && np == 1) v.en = v.cA;
-    const float rew = (float)np * v.rA - (trade ? p.cost : 0.f);
-    v.er += rew;
-    int t1 = v.t + 1;
-    const bool done = (t1 - v.es) >= p.ep_len;
-    float fin = 0.f;
-    if (done) {
-      v.eps += 1;
-      v.lr = v.er;
-      fin = v.er;
-      v.es = min((int)(u[2] * (float)(p.T - p.ep_len - 1)), p.T - p.ep_len - 2);
-      t1 = v.es;
-      v.pz = 0;
-      v.er = 0.f;
-    } else {
-      v.pz = np;
-    }
-    v.t = t1;
-    uint4 fx = v.fB;
-    float cx = v.cB, rx = v.rB;
-    if (__builtin_amdgcn_ballot_w64(done) != 0ull) {
-      const size_t o = (size_t)me * p.T + v.t;
-      const uint4 fr = bar_feat(p, me, v.t);
-      const float cr = p.close[o], rr = p.ret[o];
-      fx.x = done ? fr.x : fx.x;   // per component: a uint4 ternary lowers to a stack select
-      fx.y = done ? fr.y : fx.y;
-      fx.z = done ? fr.z : fx.z;
-      fx.w = done ? fr.w : fx.w;
-      cx = done ? cr : cx;
-      rx = done ? rr : rx;
-    }
+    gru_q_row(sWq, sQp, lane & (RN - 1), q);
+    const ActStep st = act_step(p, v, q, sU[s * RN + (lane & (RN - 1))]);
+    uint4 fx;
+    float cx, rx;
+    act_next_bar(p, v, me, st.done, fx, cx, rx);
     if (writer) {
       const size_t sl_ = v.slot;
       if (valid) {
-        p.ra[sl_ * S + s] = (unsigned char)a;
-        p.rr[sl_ * S + s] = rew;
-        p.rd[sl_ * S + s] = done ? 1 : 0;
+        p.ra[sl_ * S + s] = (unsigned char)st.a;
+        p.rr[sl_ * S + s] = st.rew;
+        p.rd[sl_ * S + s] = st.done ? 1 : 0;
       }
-      build_x(p, fx, cx, v.t, v.es, v.pz, v.en,
-              reinterpret_cast<bf16_t*>(sb + Act2Lds::X) + nxt * RN * XS + lane * XS,
+      build_x(p, fx, cx, v, reinterpret_cast<bf16_t*>(sb + Act2Lds::X) + nxt * RN * XS + lane * XS,
               valid ? p.rx + (sl_ * (size_t)(S + 1) + (size_t)(s + 1)) * RF : nullptr);
-      sDone[lane] = done ? 1 : 0;
-      if (done) {
+      sDone[lane] = st.done ? 1 : 0;
+      if (st.done) {
         uint4* hz = reinterpret_cast<uint4*>(sb + Act2Lds::H8 + nxt * RN * HS + lane * HS);
         const uint4 z = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -880,13 +671,13 @@ __global__ void __launch_bounds__(RT, 1) gru_act_pair_kernel(GruAct p) {
       }
       if (valid && p.q_out && s == S - 1) {
         float* qo = p.q_out + (size_t)me * 4;
-        qo[0] = q[0]; qo[1] = q[1]; qo[2] = q[2]; qo[3] = (float)a;
+        qo[0] = q[0]; qo[1] = q[1]; qo[2] = q[2]; qo[3] = (float)st.a;
       }
       if (valid) {
-        st_rew += rew;
-        st_exp += exploit ? 0.f : 1.f;
-        st_fin += fin;
-        st_dn += done ? 1.f : 0.f;
+        st_rew += st.rew;
+        st_exp += st.exploit ? 0.f : 1.f;
+        st_fin += st.fin;
+        st_dn += st.done ? 1.f : 0.f;
       }
     }
     v.cA = cx;
@@ -932,12 +723,7 @@ __global__ void __launch_bounds__(RT, 1) gru_act_pair_kernel(GruAct p) {
         *reinterpret_cast<float4*>(p.h + (size_t)e * RH + u0) =
             make_float4(hr[K][m][n][0], hr[K][m][n][1], hr[K][m][n][2], hr[K][m][n][3]);
       }
-    if (wave == 0 && writer) {
-      const int me = e0 + lane;
-      const ActEnv v = env_ld(sl);
-      p.pos[me] = v.t; p.ep_start[me] = v.es; p.position[me] = v.pz; p.entry[me] = v.en;
-      p.ep_ret[me] = v.er; p.episodes[me] = v.eps; p.last_ret[me] = v.lr;
-    }
+    if (wave == 0 && writer) store_env(p, e0 + lane, env_ld(sl));
   };
 
   constexpr ActSlot<0> A{};

@@ -1,5 +1,7 @@
 // Shared pieces of the GRU(256) recurrent Q-net kernels (BASELINE config 5):
-// actor (gru.hip) and fused learner (gru_learn.hip).
+// the MX-fp8 helpers of the actors (gru.hip) and the fused learner (gru_learn.hip), and, with gru_weights.h and
+// gru_net_tile.h, the one definition of the policy's bar that the actors, the backtest (gru_rollout.hip) and the
+// server (gru_serve.hip) all run.
 #pragma once
 #include "common.h"
 
@@ -90,6 +92,44 @@ ST_DEV void quant_h(const float (&hr)[2][2][4], unsigned char* sH8, int* sSc, in
           fp8x4(ldexpf(hr[m][n][0], -e), ldexpf(hr[m][n][1], -e), ldexpf(hr[m][n][2], -e), ldexpf(hr[m][n][3], -e));
     if (g4 == 0) sSc[row * SCS + wave] = e + 127;
   }
+}
+
+// ---------------------------------------------------------------- one bar of the GRU(256) policy
+// The per-bar arithmetic of the actors (gru.hip), the backtest (gru_rollout.hip) and the server (gru_serve.hip):
+// one definition, so the four kernels cannot drift apart.  A workgroup is 8 waves on a 32-env chunk; wave w owns
+// hidden units 32w .. 32w+31 of all three gates.  The callers keep their LDS layouts.
+
+// Two pieces are statements that each kernel includes in place, not functions (why: see the files): the weight
+// prologue, gru_weights.h, which declares Wh, Ws4, myWx and WqA, and the net on ONE 16-env tile n of the chunk --
+// gates from x and h, the GRU update of the tile's h in registers, this wave's Q partials -> LDS --,
+// gru_net_tile.h, included inside the kernel's `for (n = 0; n < 2; ++n)` loop.
+
+// the Q row of env `row` of the chunk: b_q + the eight waves' partials, in wave order
+ST_DEV void gru_q_row(const float* sWq, const float* sQp, int row, float (&q)[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    float v = sWq[3 * RH + a];
+#pragma unroll
+    for (int w = 0; w < RW; ++w) v += sQp[(w * 3 + a) * RN + row];
+    q[a] = v;
+  }
+}
+
+// s_waitcnt lgkmcnt(0) only, then the barrier: LDS traffic is ordered, global loads / stores stay in flight
+ST_DEV void lds_barrier() {
+  __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4));
+  asm volatile("s_barrier" ::: "memory");
+}
+
+// the epsilon-greedy draw of the backtest and the server (a served session mirrors a rollout env): counter
+// (c0, c1, 0, "GRB1") under the actors' key; `a` is the greedy action
+constexpr uint32_t TAG_ROLLOUT = 0x47524231u;
+ST_DEV int eps_greedy_draw(int a, uint32_t c0, uint32_t c1, uint32_t key0, uint32_t key1, float eps) {
+  uint32_t c2 = 0u, c3 = TAG_ROLLOUT;
+  philox4x32(c0, c1, c2, c3, key0, key1);
+  const bool exploit = u24(c0) < eps;
+  const int rnd = min((int)(u24(c1) * 3.0f), 2);
+  return exploit ? a : rnd;
 }
 
 }  // namespace st

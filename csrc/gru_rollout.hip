@@ -1,9 +1,9 @@
 // Backtest of a frozen GRU(256) policy on CDNA4 (gfx950): whole episodes of the minute-bar env in one launch.
 //
-// For env e and bar t = start .. start + steps - 1 the arithmetic of a bar is gru_act_kernel's (csrc/gru.hip)
-// on the weights st_gru_pack produced: x row (bf16) -> W_ih x on the bf16 16x16x32 MFMA, W_hh h on the MX-fp8
-// 16x16x128 scaled MFMA (quant_h / mx_mfma_sel of gru_common.h), sigm_ps / tanh_ps gates, Q = W_q bf16(h') +
-// b_q on the bf16 MFMA -- no rounding point of its own.  What differs is what surrounds it:
+// For env e and bar t = start .. start + steps - 1 the arithmetic of a bar is the actors' (csrc/gru.hip) on the
+// weights st_gru_pack produced, from the same source: the statements of gru_weights.h and gru_net_tile.h,
+// gru_q_row / quant_h of gru_common.h and the trading rule of minute_rule.h; no rounding point of its own.
+// What differs is what surrounds it:
 //  * a workgroup (8 waves, 32 envs) owns its envs for the whole launch: h (fp32, accumulator layout), the
 //    position, entry price and running return never leave the chip; the weights are loaded once;
 //  * every env is at the same bar, so episode ends (consecutive ep_len-bar stretches from `origin`) are
@@ -44,8 +44,6 @@ struct GruRollout {
   uint32_t key0, key1, env_offset;   // draw counter: (env_offset + e, t, 0, "GRB1")
 };
 
-constexpr uint32_t TAG_ROLLOUT = 0x47524231u;
-
 struct Lds {
   static constexpr int WX = 0;                                   // RW*6*64 s8v
   static constexpr int X = WX + RW * 6 * 64 * 16;                // [2][RN*XS] bf16
@@ -59,12 +57,6 @@ struct Lds {
 static_assert(Lds::BYTES <= 160 * 1024, "rollout LDS");
 static_assert(Lds::X % 16 == 0 && Lds::H8 % 16 == 0 && Lds::SC % 16 == 0 && Lds::B % 16 == 0, "16-byte carves");
 
-// s_waitcnt lgkmcnt(0) only, then the barrier: LDS traffic is ordered, global loads / stores stay in flight
-ST_DEV void bar() {
-  __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4));
-  asm volatile("s_barrier" ::: "memory");
-}
-
 __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const s8v* sWx = reinterpret_cast<const s8v*>(lds + Lds::WX);
@@ -77,34 +69,7 @@ __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
 
   const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int i = tid; i < RW * 6 * 64; i += RT) reinterpret_cast<s8v*>(lds + Lds::WX)[i] = p.wih[i];
-  for (int i = tid; i < 4 * RH; i += RT) {
-    sB[i] = p.bias4[i];
-    sWq[i] = p.wq[i];
-  }
-  // resident MX-fp8 W_hh fragments of this wave's 32 units x 3 gates (as gru_act_kernel)
-  i8v Wh[3][2][2];
-  int Ws4[3] = {0, 0, 0};
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int idx = (((wave * 3 + g) * 2 + m) * 2 + ks) * 64 + lane;
-        Wh[g][m][ks] = p.whh8[idx];
-        Ws4[g] |= (p.whhs[idx] & 0xFF) << (8 * (2 * m + ks));
-      }
-  const s8v* myWx = sWx + wave * 6 * 64 + lane;
-  s8v WqA;
-  {
-    const int a = l16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int u = 32 * wave + (j < 4 ? 4 * g4 + j : 16 + 4 * g4 + j - 4);
-      WqA[j] = (short)f2bf(a < 3 ? p.wq[a * RH + u] : 0.f);
-    }
-  }
+#include "gru_weights.h"
   const bool greedy = __builtin_isinf(p.eps);
   const int nchunks = (p.E + RN - 1) / RN, steps = p.steps;
   // start of the episode that holds bar `start` (origin <= start)
@@ -146,7 +111,7 @@ __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
       const uint4 f0 = *reinterpret_cast<const uint4*>(p.feat + o * RMF);
       if (writer) minute_x_row(sX + lane * XS, f0, minute_x_env(pz_, en_, cA, p.start - es0, p.inv_ep_len));
     }
-    bar();
+    lds_barrier();
 
     int es = es0;
 #pragma unroll 1
@@ -159,62 +124,10 @@ __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
       const int* cS = sSc + cur * RN * SCS;
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
-        f4v ar[2], az[2], anx[2], anh[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          const int u0 = 32 * wave + 16 * m + 4 * g4;
-          ar[m] = *reinterpret_cast<const f4v*>(sB + u0);
-          az[m] = *reinterpret_cast<const f4v*>(sB + RH + u0);
-          anx[m] = *reinterpret_cast<const f4v*>(sB + 2 * RH + u0);
-          anh[m] = *reinterpret_cast<const f4v*>(sB + 3 * RH + u0);
-        }
-        const int row = 16 * n + l16;
-        {
-          const s8v xb = lds_ld8(cX + row * XS + 8 * g4);
-#pragma unroll
-          for (int m = 0; m < 2; ++m) {
-            ar[m] = mfma32(myWx[(0 * 2 + m) * 64], xb, ar[m]);
-            az[m] = mfma32(myWx[(1 * 2 + m) * 64], xb, az[m]);
-            anx[m] = mfma32(myWx[(2 * 2 + m) * 64], xb, anx[m]);
-          }
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const uint4 h0 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 16 * g4);
-          const uint4 h1 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 64 + 16 * g4);
-          i8v hb;
-          hb[0] = (int)h0.x; hb[1] = (int)h0.y; hb[2] = (int)h0.z; hb[3] = (int)h0.w;
-          hb[4] = (int)h1.x; hb[5] = (int)h1.y; hb[6] = (int)h1.z; hb[7] = (int)h1.w;
-          const int sc = cS[row * SCS + 4 * ks + g4];
-#define ST_MX3R(M, KS)                                                             \
-  ar[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[0][M][KS], hb, ar[M], Ws4[0], sc);          \
-  az[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[1][M][KS], hb, az[M], Ws4[1], sc);          \
-  anh[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[2][M][KS], hb, anh[M], Ws4[2], sc);
-          if (ks == 0) { ST_MX3R(0, 0) ST_MX3R(1, 0) } else { ST_MX3R(0, 1) ST_MX3R(1, 1) }
-#undef ST_MX3R
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float r = sigm_ps(ar[m][i]);
-            const float z = sigm_ps(az[m][i]);
-            const float nn = tanh_ps(__builtin_fmaf(r, anh[m][i], anx[m][i]));
-            hr[m][n][i] = __builtin_fmaf(z, hr[m][n][i] - nn, nn);
-          }
-        {
-          s8v hb;
-          const uint32_t p0 = pack_bf2(hr[0][n][0], hr[0][n][1]), p1 = pack_bf2(hr[0][n][2], hr[0][n][3]);
-          const uint32_t p2 = pack_bf2(hr[1][n][0], hr[1][n][1]), p3 = pack_bf2(hr[1][n][2], hr[1][n][3]);
-          hb[0] = (short)(p0 & 0xFFFF); hb[1] = (short)(p0 >> 16); hb[2] = (short)(p1 & 0xFFFF); hb[3] = (short)(p1 >> 16);
-          hb[4] = (short)(p2 & 0xFFFF); hb[5] = (short)(p2 >> 16); hb[6] = (short)(p3 & 0xFFFF); hb[7] = (short)(p3 >> 16);
-          const f4v qp = mfma32(WqA, hb, zero4());
-          if (g4 == 0) {
-            sQp[(wave * 3 + 0) * RN + row] = qp[0];
-            sQp[(wave * 3 + 1) * RN + row] = qp[1];
-            sQp[(wave * 3 + 2) * RN + row] = qp[2];
-          }
-        }
+        float (&hrt)[2][2][4] = hr;
+#define GRU_TILE_STAMP
+#include "gru_net_tile.h"
+#undef GRU_TILE_STAMP
       }
       // an episode's last bar: the next one starts from h = 0 (Q of this bar is already taken)
       if (done) {
@@ -226,25 +139,13 @@ __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
             for (int i = 0; i < 4; ++i) hr[m][n][i] = 0.f;
       }
       quant_h(hr, sH8 + nxt * RN * HS, sSc + nxt * RN * SCS, wave, l16, g4);
-      bar();
+      lds_barrier();
       // ---------------------------------------------------------- env step (wave 0)
       if (wave == 0) {
         float q[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          float v = sWq[3 * RH + a];
-#pragma unroll
-          for (int w = 0; w < RW; ++w) v += sQp[(w * 3 + a) * RN + row_];
-          q[a] = v;
-        }
+        gru_q_row(sWq, sQp, row_, q);
         int a = first_max3(q[0], q[1], q[2]);
-        if (!greedy) {
-          uint32_t c0 = p.env_offset + (uint32_t)(e0 + row_), c1 = (uint32_t)t, c2 = 0u, c3 = TAG_ROLLOUT;
-          philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-          const bool exploit = u24(c0) < p.eps;
-          const int rnd = min((int)(u24(c1) * 3.0f), 2);
-          a = exploit ? a : rnd;
-        }
+        if (!greedy) a = eps_greedy_draw(a, p.env_offset + (uint32_t)(e0 + row_), (uint32_t)t, p.key0, p.key1, p.eps);
         const MinuteMove mv = minute_move(a, pz_, en_, cA, rA, p.cost);
         sum_ += mv.reward;
         ntr_ += mv.trade ? 1 : 0;
@@ -273,7 +174,7 @@ __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
         rB = p.ret[o1];
         fB = *reinterpret_cast<const uint4*>(p.feat + o1 * RMF);
       }
-      bar();
+      lds_barrier();
       if (done) es = t + 1;
     }
     // results
@@ -296,7 +197,7 @@ __global__ void __launch_bounds__(RT, 1) gru_rollout_kernel(GruRollout p) {
       p.out_position[e] = pz_;
       p.out_entry[e] = en_;
     }
-    bar();
+    lds_barrier();
   }
 }
 

@@ -3,7 +3,9 @@
 // A session is a slot of a device-resident table: h [S][RH] fp32 and one 64-byte scalar record per slot
 // (ServeRec).  A request row names its slot and brings the bar (8 bf16 features, close).  The arithmetic of a
 // row is exactly one bar of gru_rollout_kernel (csrc/gru_rollout.hip) on the weights st_gru_pack produced -- the
-// same helpers in the same order, no rounding point of its own.  What differs is what surrounds the bar:
+// same source (gru_weights.h, gru_net_tile.h, gru_common.h, the trading rule of minute_rule.h), no rounding point
+// of its own.
+// What differs is what surrounds the bar:
 //  * h and the scalars are gathered by slot and scattered back to it; a row whose slot is outside [0, S) (-1 is
 //    the padding value) or past B loads nothing from the table, stores nothing and answers action -1;
 //  * the episode state is per row: done = elapsed + 1 >= ep_len flattens that row at no cost, clears its entry,
@@ -60,8 +62,6 @@ struct ServeRec {
 };
 static_assert(sizeof(ServeRec) == 44 && sizeof(ServeRec) <= REC * 4, "record layout");
 
-constexpr uint32_t TAG_ROLLOUT = 0x47524231u;   // the backtest's draws: a served session mirrors a rollout env
-
 struct Lds {
   static constexpr int WX = 0;                                   // RW*6*64 s8v
   static constexpr int X = WX + RW * 6 * 64 * 16;                // [RN*XS] bf16
@@ -75,12 +75,6 @@ struct Lds {
 };
 static_assert(Lds::BYTES <= 160 * 1024, "serve LDS");
 static_assert(Lds::X % 16 == 0 && Lds::H8 % 16 == 0 && Lds::SC % 16 == 0 && Lds::B % 16 == 0, "16-byte carves");
-
-// s_waitcnt lgkmcnt(0) only, then the barrier: LDS traffic is ordered, global loads / stores stay in flight
-ST_DEV void bar() {
-  __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4));
-  asm volatile("s_barrier" ::: "memory");
-}
 
 // a chunk's request rows and table rows as the lanes hold them
 struct Stage {
@@ -137,34 +131,7 @@ __global__ void __launch_bounds__(RT, 1) gru_serve_kernel(GruServe p) {
 
   const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (int i = tid; i < RW * 6 * 64; i += RT) reinterpret_cast<s8v*>(lds + Lds::WX)[i] = p.wih[i];
-  for (int i = tid; i < 4 * RH; i += RT) {
-    sB[i] = p.bias4[i];
-    sWq[i] = p.wq[i];
-  }
-  // resident MX-fp8 W_hh fragments of this wave's 32 units x 3 gates (as gru_act_kernel)
-  i8v Wh[3][2][2];
-  int Ws4[3] = {0, 0, 0};
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int idx = (((wave * 3 + g) * 2 + m) * 2 + ks) * 64 + lane;
-        Wh[g][m][ks] = p.whh8[idx];
-        Ws4[g] |= (p.whhs[idx] & 0xFF) << (8 * (2 * m + ks));
-      }
-  const s8v* myWx = sWx + wave * 6 * 64 + lane;
-  s8v WqA;
-  {
-    const int a = l16;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int u = 32 * wave + (j < 4 ? 4 * g4 + j : 16 + 4 * g4 + j - 4);
-      WqA[j] = (short)f2bf(a < 3 ? p.wq[a * RH + u] : 0.f);
-    }
-  }
+#include "gru_weights.h"
   const bool greedy = __builtin_isinf(p.eps);
   const int nchunks = (p.B + RN - 1) / RN;
   const int row_ = lane & (RN - 1);
@@ -247,67 +214,18 @@ __global__ void __launch_bounds__(RT, 1) gru_serve_kernel(GruServe p) {
         sDn[lane] = done_ ? 1 : 0;
       }
     }
-    bar();
+    lds_barrier();
 
-    // ------------------------------------------------ the bar's net (gru_rollout_kernel's, one step)
+    // ------------------------------------------------ the bar's net
+    const bf16_t* cX = sX;
+    const unsigned char* cH = sH8;
+    const int* cS = sSc;
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      f4v ar[2], az[2], anx[2], anh[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int u0 = 32 * wave + 16 * m + 4 * g4;
-        ar[m] = *reinterpret_cast<const f4v*>(sB + u0);
-        az[m] = *reinterpret_cast<const f4v*>(sB + RH + u0);
-        anx[m] = *reinterpret_cast<const f4v*>(sB + 2 * RH + u0);
-        anh[m] = *reinterpret_cast<const f4v*>(sB + 3 * RH + u0);
-      }
-      const int row = 16 * n + l16;
-      {
-        const s8v xb = lds_ld8(sX + row * XS + 8 * g4);
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          ar[m] = mfma32(myWx[(0 * 2 + m) * 64], xb, ar[m]);
-          az[m] = mfma32(myWx[(1 * 2 + m) * 64], xb, az[m]);
-          anx[m] = mfma32(myWx[(2 * 2 + m) * 64], xb, anx[m]);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const uint4 h0 = *reinterpret_cast<const uint4*>(sH8 + row * HS + 128 * ks + 16 * g4);
-        const uint4 h1 = *reinterpret_cast<const uint4*>(sH8 + row * HS + 128 * ks + 64 + 16 * g4);
-        i8v hb;
-        hb[0] = (int)h0.x; hb[1] = (int)h0.y; hb[2] = (int)h0.z; hb[3] = (int)h0.w;
-        hb[4] = (int)h1.x; hb[5] = (int)h1.y; hb[6] = (int)h1.z; hb[7] = (int)h1.w;
-        const int sc = sSc[row * SCS + 4 * ks + g4];
-#define ST_MX3R(M, KS)                                                             \
-  ar[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[0][M][KS], hb, ar[M], Ws4[0], sc);          \
-  az[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[1][M][KS], hb, az[M], Ws4[1], sc);          \
-  anh[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[2][M][KS], hb, anh[M], Ws4[2], sc);
-        if (ks == 0) { ST_MX3R(0, 0) ST_MX3R(1, 0) } else { ST_MX3R(0, 1) ST_MX3R(1, 1) }
-#undef ST_MX3R
-      }
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float r = sigm_ps(ar[m][i]);
-          const float z = sigm_ps(az[m][i]);
-          const float nn = tanh_ps(__builtin_fmaf(r, anh[m][i], anx[m][i]));
-          hr[m][n][i] = __builtin_fmaf(z, hr[m][n][i] - nn, nn);
-        }
-      {
-        s8v hb;
-        const uint32_t p0 = pack_bf2(hr[0][n][0], hr[0][n][1]), p1 = pack_bf2(hr[0][n][2], hr[0][n][3]);
-        const uint32_t p2 = pack_bf2(hr[1][n][0], hr[1][n][1]), p3 = pack_bf2(hr[1][n][2], hr[1][n][3]);
-        hb[0] = (short)(p0 & 0xFFFF); hb[1] = (short)(p0 >> 16); hb[2] = (short)(p1 & 0xFFFF); hb[3] = (short)(p1 >> 16);
-        hb[4] = (short)(p2 & 0xFFFF); hb[5] = (short)(p2 >> 16); hb[6] = (short)(p3 & 0xFFFF); hb[7] = (short)(p3 >> 16);
-        const f4v qp = mfma32(WqA, hb, zero4());
-        if (g4 == 0) {
-          sQp[(wave * 3 + 0) * RN + row] = qp[0];
-          sQp[(wave * 3 + 1) * RN + row] = qp[1];
-          sQp[(wave * 3 + 2) * RN + row] = qp[2];
-        }
-      }
+      float (&hrt)[2][2][4] = hr;
+#define GRU_TILE_STAMP
+#include "gru_net_tile.h"
+#undef GRU_TILE_STAMP
     }
     // The prefetch has had the whole net phase to land, and this chunk's stores are not issued yet: wait for
     // it here (vmcnt(0)), so that the stores below are never waited for before they too have had a net phase
@@ -325,25 +243,13 @@ __global__ void __launch_bounds__(RT, 1) gru_serve_kernel(GruServe p) {
               dn ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(hr[m][n][0], hr[m][n][1], hr[m][n][2], hr[m][n][3]);
         }
       }
-    bar();
+    lds_barrier();
     // ------------------------------------------------ env step (wave 0)
     if (wave == 0) {
       float q[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        float v = sWq[3 * RH + a];
-#pragma unroll
-        for (int w = 0; w < RW; ++w) v += sQp[(w * 3 + a) * RN + row_];
-        q[a] = v;
-      }
+      gru_q_row(sWq, sQp, row_, q);
       int a = first_max3(q[0], q[1], q[2]);
-      if (!greedy) {
-        uint32_t c0 = draw_, c1 = bars_, c2 = 0u, c3 = TAG_ROLLOUT;
-        philox4x32(c0, c1, c2, c3, p.key0, p.key1);
-        const bool exploit = u24(c0) < p.eps;
-        const int rnd = min((int)(u24(c1) * 3.0f), 2);
-        a = exploit ? a : rnd;
-      }
+      if (!greedy) a = eps_greedy_draw(a, draw_, bars_, p.key0, p.key1, p.eps);
       // the move alone: this bar's reward waits for the next close
       const MinuteMove mv = minute_move(a, pz_, en_, c_, 0.f, p.cost);
       const int row = r0 + lane;
@@ -384,8 +290,8 @@ __global__ void __launch_bounds__(RT, 1) gru_serve_kernel(GruServe p) {
         }
       }
     }
-    // the next bar() (after the next chunk's x row and fp8 tile are written) orders this phase's LDS reads
-    // before the next net phase's writes; the tile and x row themselves were last read before the bar() above
+    // the next lds_barrier() (after the next chunk's x row and fp8 tile are written) orders this phase's LDS reads
+    // before the next net phase's writes; the tile and x row themselves were last read before the barrier above
     cur = nxt;
     sl[0] = nsl[0]; sl[1] = nsl[1]; sle = nsle;
     nsl[0] = fsl[0]; nsl[1] = fsl[1]; nsle = fsle;

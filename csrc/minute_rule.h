@@ -1,7 +1,7 @@
 // The minute-bar trading env (BASELINE config 5) as functions of scalars: the position / reward step and the
 // env half of the x row.  Host mirror: sharetrade/env/minute.py (same float32 operations in the same order;
-// the build keeps -ffp-contract=off, so nothing here fuses).  Written for csrc/gru_rollout.hip; the actors of
-// csrc/gru.hip carry the same arithmetic inline and can adopt these.
+// the build keeps -ffp-contract=off, so nothing here fuses).  Used by the actors of csrc/gru.hip, the backtest
+// (csrc/gru_rollout.hip) and the server (csrc/gru_serve.hip).
 #pragma once
 #include "common.h"
 
