@@ -388,6 +388,10 @@ struct GruSeqBwd {
   float* gwq;           // [3][RH]   (+= ; zeroed by the host each update)
   float* gbq;           // [3]
   int B, S;
+  // 0: every workgroup adds into the one gwq / gbq (atomics: the sum's bits depend on the arrival order).
+  // > 0: workgroup b adds into gwq + b * gq_stride and gbq + b * gq_stride, its own zeroed row of a partials
+  // buffer, and gru_qgrad_reduce_kernel sums the rows in order (RecurrentDQN(deterministic=True))
+  int gq_stride;
 };
 
 constexpr int GQS = RG + 16;      // dGh fp8 tile row stride (bytes): 784, conflict-free b128 reads
@@ -626,9 +630,10 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_bwd_kernel(GruSeqBwd p) {
       const int u = 32 * wave + 16 * m + 4 * g4 + i;
       const float v0 = row16_sum(gq[0][m][i]), v1 = row16_sum(gq[1][m][i]), v2 = row16_sum(gq[2][m][i]);
       if (l16 == 0) {
-        atomicAdd(p.gwq + u, v0);
-        atomicAdd(p.gwq + RH + u, v1);
-        atomicAdd(p.gwq + 2 * RH + u, v2);
+        float* gw = p.gwq + (size_t)blockIdx.x * p.gq_stride;
+        atomicAdd(gw + u, v0);
+        atomicAdd(gw + RH + u, v1);
+        atomicAdd(gw + 2 * RH + u, v2);
       }
     }
   if (wave == 0) {
@@ -636,11 +641,23 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_bwd_kernel(GruSeqBwd p) {
     gbq1 = wave_sum(gbq1);
     gbq2 = wave_sum(gbq2);
     if (lane == 0) {
-      atomicAdd(p.gbq + 0, gbq0);
-      atomicAdd(p.gbq + 1, gbq1);
-      atomicAdd(p.gbq + 2, gbq2);
+      float* gb = p.gbq + (size_t)blockIdx.x * p.gq_stride;
+      atomicAdd(gb + 0, gbq0);
+      atomicAdd(gb + 1, gbq1);
+      atomicAdd(gb + 2, gbq2);
     }
   }
+}
+
+// The ordered sum of the backward workgroups' W_q / b_q gradient rows (GruSeqBwd::gq_stride > 0): part is
+// [rows][stride] with a row = [3][RH] of gwq, then 3 of gbq; one thread per value, rows added in index order.
+__global__ void __launch_bounds__(256) gru_qgrad_reduce_kernel(const float* __restrict__ part, int rows, int stride,
+                                                               float* gwq, float* gbq) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 3 * RH + 3) return;
+  float s = 0.f;
+  for (int b = 0; b < rows; ++b) s += part[(size_t)b * stride + i];
+  if (i < 3 * RH) gwq[i] = s; else gbq[i - 3 * RH] = s;
 }
 
 // Gradient fix-up after the weight-gradient GEMMs (one launch instead of four strided copies):
@@ -686,6 +703,7 @@ extern "C" hipError_t st_gru_td(const st::GruTD* p, hipStream_t s) {
 
 extern "C" hipError_t st_gru_seq_bwd(const st::GruSeqBwd* p, hipStream_t s) {
   if (p->B % st::LB || p->S <= 0 || p->S > 64) return hipErrorInvalidValue;
+  if (p->gq_stride < 0 || (p->gq_stride > 0 && p->gq_stride < 3 * st::RH + 3)) return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
     hipError_t e = hipFuncSetAttribute((const void*)st::gru_seq_bwd_kernel,
@@ -694,6 +712,17 @@ extern "C" hipError_t st_gru_seq_bwd(const st::GruSeqBwd* p, hipStream_t s) {
     attr = true;
   }
   hipLaunchKernelGGL(st::gru_seq_bwd_kernel, dim3(p->B / st::LBB), dim3(st::RT), st::BwdLds::BYTES, s, *p);
+  return hipGetLastError();
+}
+
+extern "C" int st_gru_seq_bwd_rows() { return st::LBB; }   // sequences per backward workgroup
+
+extern "C" hipError_t st_gru_qgrad_reduce(const float* part, int rows, int stride, float* gwq, float* gbq,
+                                          hipStream_t s) {
+  if (part == nullptr || gwq == nullptr || gbq == nullptr || rows < 1 || stride < 3 * st::RH + 3)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(st::gru_qgrad_reduce_kernel, dim3((3 * st::RH + 3 + 255) / 256), dim3(256), 0, s, part, rows,
+                     stride, gwq, gbq);
   return hipGetLastError();
 }
 

@@ -6,14 +6,16 @@ Commands
             price service -> router -> workers -> learner; prints avg/std.
 ``engine``  run the vectorised engine directly for N steps and print metrics.
 ``deep``    train the 4x1024-MLP replay DQN (BASELINE config 4) for N iterations.
-``recurrent`` train the GRU(256) minute-bar DQN (BASELINE config 5) for N iterations.
+``recurrent`` train the GRU(256) minute-bar DQN (BASELINE config 5) for N iterations; with ``--bars-file F`` on the
+            first ``--train-frac`` of every series of a file of raw OHLCV minute bars (``data.ohlcv``).
 ``serve``   serve SelectionAction over HTTP from the batched GPU kernel (weights from an
             engine checkpoint or random init).  With a checkpoint of a ``recurrent`` run (or ``--policy gru``):
             stateful GRU(256) sessions, one minute bar per request (``/session`` routes).
 ``backtest`` what a policy (engine checkpoint or random init) would have done over a price history: a CSV
             series or N synthetic ones, one rollout launch; prints policy vs buy-and-hold vs uniform random.
             With a checkpoint of a ``recurrent`` run (or ``--policy gru``): the GRU(256) policy, greedy, on N
-            held-out synthetic minute-bar series; prints policy vs always-long vs uniform random vs flat.
+            held-out synthetic minute-bar series, or (``--bars-file F [--held-out]``) on the raw OHLCV minute bars of
+            a file; prints policy vs always-long vs uniform random vs flat.
 ``config``  print the resolved configuration (JSON).
 
 Common flags: ``--preset {reference_compat,intended,flagship,flagship_stable,test}``,
@@ -88,9 +90,83 @@ def _gru_path(a) -> bool:
     return checkpoint_kind(a.ckpt) == "recurrent"
 
 
+def _first_session(bars) -> int:
+    """Bars of the first session of series 0 (to the first later bar with minute 0)."""
+    N, T = bars.shape
+    if bars.minute is None:
+        return T
+    import numpy as np
+
+    m = np.asarray(bars.minute)
+    m = m[0] if m.ndim == 2 else m
+    later = np.nonzero(m[1:] == 0)[0]
+    return int(later[0]) + 1 if later.size else T
+
+
+def _file_bars(a, dev, meta):
+    """``--bars-file``: the file's bars featurised with the checkpoint's parameters (``meta["bar_features"]``), or
+    with ones fitted on the file's first session.  Returns (close, feat, info)."""
+    import numpy as np
+    import torch
+
+    from .data import ohlcv as ov
+
+    bars = ov.load_bars(a.bars_file)
+    N, T = bars.shape
+    bf = (meta or {}).get("bar_features")
+    if bf:
+        fp = ov.FeatureParams.from_meta(bf)
+        if fp.sigma.shape[0] != N:
+            raise ValueError(f"the checkpoint holds feature parameters of {fp.sigma.shape[0]} series, "
+                             f"{a.bars_file} has {N}")
+        source = "checkpoint"
+    else:
+        upto = _first_session(bars)
+        fp = ov.fit_feature_params(bars, upto=upto)
+        source = "first_session"
+        print(f"warning: no feature parameters in a checkpoint; fitted on the first {upto} bars of {a.bars_file}",
+              file=sys.stderr)
+    start = 0
+    if a.held_out:
+        frac = float(bf["train_frac"]) if bf else float(a.train_frac)
+        start = int(T * frac)
+        if T - start < 2:
+            raise ValueError(f"no held-out bars after train_frac={frac}")
+    # the filter runs from the first bar on, so the held-out part starts with the state the training part left
+    if dev.type == "cuda":
+        r = ov.featurise_gpu(bars, fp, dev)
+        close, feat = r.close[:, start:].contiguous(), r.feat[:, start:].contiguous()
+    else:
+        r = ov.featurise_numpy(bars, fp)
+        close = torch.from_numpy(np.ascontiguousarray(r.close[:, start:]))
+        feat = torch.from_numpy(np.ascontiguousarray(r.feat[:, start:])).to(torch.bfloat16)
+    return close, feat, {"bars_file": a.bars_file, "held_out": bool(a.held_out), "first_bar": start,
+                         "feature_params": source}
+
+
+def _recurrent_bank(a, cfg: Config, ctx, kw: dict) -> dict:
+    """``recurrent --bars-file``: featurise the first ``--train-frac`` of every series with parameters fitted on
+    that part, cut this rank's windows (``seed + rank``) into ``kw["bank"]``; returns the checkpoint meta entry."""
+    from .data import ohlcv as ov
+
+    if not 0.0 < a.train_frac <= 1.0:
+        raise ValueError("--train-frac must be in (0, 1]")
+    bars = ov.load_bars(a.bars_file)
+    N, T = bars.shape
+    upto = int(T * a.train_frac)
+    fp = ov.fit_feature_params(bars, upto=upto)
+    r = ov.featurise_gpu(bars.piece(0, upto), fp, ctx.device)
+    E = int(kw.get("envs", 65536))
+    kw["bars"] = min(4096, upto)
+    kw["bank"] = ov.window_bank(r.close, r.feat, E, kw["bars"], seed=int(cfg.agent.seed) + int(ctx.rank))
+    return {"bar_features": {**fp.to_meta(bars.names_or_default()), "crc32c": ov.file_crc32c(a.bars_file),
+                             "train_frac": float(a.train_frac), "file": a.bars_file}}
+
+
 def _backtest_gru(a, cfg: Config) -> dict:
-    """``backtest`` of a GRU(256) policy on N held-out synthetic minute-bar series: the greedy policy, always
-    long (Buy on every bar), uniform random and flat, each as mean / std / median of the per-series return."""
+    """``backtest`` of a GRU(256) policy on N held-out synthetic minute-bar series (or the bars of ``--bars-file``):
+    the greedy policy, always long (Buy on every bar), uniform random and flat, each as mean / std / median of the
+    per-series return."""
     import os
 
     import numpy as np
@@ -106,14 +182,23 @@ def _backtest_gru(a, cfg: Config) -> dict:
         pol = GruPolicy.from_checkpoint(a.ckpt, device=dev)
     else:
         pol = GruPolicy(gq.init_params(cfg.agent.seed), device=dev, seed=cfg.agent.seed)
-    N, ep_len = int(a.synthetic), int(a.ep_len)
-    T = int(a.bars) if a.bars else 4 * ep_len + 1
-    bars_seed = pol.seed + 1000 if a.bars_seed is None else int(a.bars_seed)
-    if dev.type == "cuda":
-        close, feat = mb.generate_gpu(N, T, dev, seed=bars_seed)
+    ep_len = int(a.ep_len)
+    info = {}
+    if a.bars_file:
+        from .serve.gru_rollout import checkpoint_meta
+
+        close, feat, info = _file_bars(a, dev, checkpoint_meta(a.ckpt) if a.ckpt else None)
+        N, T = (int(v) for v in close.shape)
+        bars_seed = None
     else:
-        c, f = mb.generate_numpy(N, T, seed=bars_seed)
-        close, feat = torch.from_numpy(c), torch.from_numpy(f).to(torch.bfloat16)
+        N = int(a.synthetic)
+        T = int(a.bars) if a.bars else 4 * ep_len + 1
+        bars_seed = pol.seed + 1000 if a.bars_seed is None else int(a.bars_seed)
+        if dev.type == "cuda":
+            close, feat = mb.generate_gpu(N, T, dev, seed=bars_seed)
+        else:
+            c, f = mb.generate_numpy(N, T, seed=bars_seed)
+            close, feat = torch.from_numpy(c), torch.from_numpy(f).to(torch.bfloat16)
     kw = dict(ep_len=ep_len, cost=float(a.cost))
     res = pol.backtest(close, feat, trace=bool(a.trace_out), **kw)
     steps = res.steps
@@ -127,7 +212,7 @@ def _backtest_gru(a, cfg: Config) -> dict:
         np.save(os.path.join(a.trace_out, "reward.npy"), res.reward.cpu().numpy())
     return {"policy_kind": "gru", "series": N, "bars": T, "steps": int(steps), "ep_len": ep_len, "cost": float(a.cost),
             "bars_seed": bars_seed, "backend": res.backend, "weights": "checkpoint" if a.ckpt else "init",
-            "policy": res.summary(), **base}
+            "policy": res.summary(), **base, **info}
 
 
 def main(argv=None) -> int:
@@ -187,6 +272,12 @@ def main(argv=None) -> int:
             p.add_argument("--no-graph", action="store_true")
             p.add_argument("--dist-backend", default=None, help="torch.distributed backend (default nccl = RCCL)")
             p.add_argument("--trace", default=None, help="Chrome trace output path (torch.profiler)")
+            if name == "recurrent":
+                p.add_argument("--bars-file", default=None, metavar="F",
+                               help="train on raw OHLCV minute bars: an .npz of [N, T] planes or a one-series .csv "
+                                    "(data.ohlcv.load_bars) instead of the synthetic generator's")
+                p.add_argument("--train-frac", type=float, default=0.8,
+                               help="--bars-file: the leading part of every series that is trained on")
         if name == "serve":
             p.add_argument("--ckpt", default=None, help="engine checkpoint file or directory (default: random init)")
             p.add_argument("--ckpt-root", default=None,
@@ -213,6 +304,13 @@ def main(argv=None) -> int:
             src.add_argument("--csv", default=None, help="one series: `price, yyyy-MM-dd` rows (or a parsed .npz)")
             src.add_argument("--synthetic", type=int, default=None, metavar="N",
                              help="N random-walk series of data.length days (data.* of the config)")
+            src.add_argument("--bars-file", default=None, metavar="F",
+                             help="GRU policy: raw OHLCV minute bars, an .npz of [N, T] planes or a one-series .csv of "
+                                  "`yyyy-MM-dd HH:mm,open,high,low,close,volume` rows")
+            p.add_argument("--held-out", action="store_true",
+                           help="--bars-file: only the bars after the checkpoint's train_frac")
+            p.add_argument("--train-frac", type=float, default=0.8,
+                           help="--bars-file --held-out without a checkpoint that records one")
             p.add_argument("--device", default="auto")
             p.add_argument("--trace-out", default=None, metavar="DIR",
                            help="write actions.npy and equity.npy (GRU policy: reward.npy) here")
@@ -243,6 +341,8 @@ def main(argv=None) -> int:
         res = run(cfg, engine=a.engine, device=a.device, max_prices=a.max_prices, gpus=a.gpus, dp=dp)
         print(json.dumps(res, default=str))
         return 0 if res.get("completed") else 1
+    if a.cmd == "recurrent" and a.bars_file and a.elastic:
+        ap.error("--bars-file is not supported under --elastic")
     if a.cmd in ("engine", "deep", "recurrent") and a.elastic:
         # the launcher never touches the GPU: one fresh process per rank (parallel/elastic_cli.py)
         from .parallel.elastic_cli import run_elastic
@@ -296,6 +396,8 @@ def main(argv=None) -> int:
 
         # under torch.distributed.run: one rank per GPU, synchronous data parallel over RCCL
         ctx = D.init(backend=a.dist_backend, device="cuda")
+        if a.cmd == "recurrent" and a.bars_file:
+            kw["extra_meta"] = _recurrent_bank(a, cfg, ctx, kw)
         res = run_learner(a.cmd, cfg, a.iterations, device=ctx.device, metrics_path=a.metrics,
                           log_every=a.log_every, ckpt_dir=a.ckpt_dir, ckpt_every=a.ckpt_every, resume=a.resume,
                           graph=not a.no_graph, ctx=ctx, trace_path=a.trace, **kw)
@@ -341,10 +443,12 @@ def main(argv=None) -> int:
     if a.cmd == "backtest":
         if _gru_path(a):
             if a.csv:
-                ap.error("backtest of a GRU policy: --csv is not supported (the CSV format has no bar features); "
-                         "use --synthetic N")
+                ap.error("backtest of a GRU policy: --csv holds daily prices, not minute bars; use --bars-file F "
+                         "(raw OHLCV minute bars) or --synthetic N")
             print(json.dumps(_backtest_gru(a, cfg)))
             return 0
+        if a.bars_file:
+            ap.error("--bars-file is for a GRU policy (--policy gru or a checkpoint of a `recurrent` run)")
         print(json.dumps(_backtest(a, cfg)))
         return 0
     if a.cmd == "engine":

@@ -44,7 +44,14 @@ class BarParams:
 
 def generate_numpy(E: int, T: int, bp: BarParams = BarParams(), seed: int = 0) -> Tuple[np.ndarray, np.ndarray]:
     """(close [E, T] float32, feat [E, T, 8] float32) — float32 host reference of the kernel."""
+    return _generate_numpy(E, T, bp, seed, None)
+
+
+def _generate_numpy(E: int, T: int, bp: BarParams, seed: int, ohlv) -> Tuple[np.ndarray, np.ndarray]:
+    """``generate_numpy``; ``ohlv``: None, or a dict that receives the bars' ``open`` / ``high`` / ``low`` /
+    ``volume`` planes [E, T] float32 (``data.ohlcv.generate_ohlcv_numpy``)."""
     f = np.float32
+    planes = None if ohlv is None else {k: np.zeros((E, T), np.float32) for k in ("open", "high", "low", "volume")}
     k0, k1 = rng.key_for(seed, 0)
     e = np.arange(E, dtype=np.uint32)
     c0, _, _, _ = rng.philox4x32(e, np.full(E, 0xFFFFFFFF, np.uint32), np.zeros(E, np.uint32),
@@ -87,6 +94,8 @@ def generate_numpy(E: int, T: int, bp: BarParams = BarParams(), seed: int = 0) -
         rprev = ret
         ang = twopi * f(tod) / f(bp.day)
         close[:, t] = c
+        if planes is not None:
+            planes["open"][:, t], planes["high"][:, t], planes["low"][:, t], planes["volume"][:, t] = opn, hi, lo, vol
         feat[:, t, 0] = ret * f(100)
         feat[:, t, 1] = (hi - lo) / c * f(100)
         feat[:, t, 2] = (c - lo) / np.maximum(hi - lo, f(1e-12)) - f(0.5)
@@ -95,6 +104,8 @@ def generate_numpy(E: int, T: int, bp: BarParams = BarParams(), seed: int = 0) -
         feat[:, t, 5] = np.cos(ang)
         feat[:, t, 6] = mom * f(100)
         feat[:, t, 7] = sig * f(100)
+    if planes is not None:
+        ohlv.update(planes)
     return close, feat
 
 

@@ -120,7 +120,7 @@ class TDArgs(C.Structure):
 class SeqBwdArgs(C.Structure):
     _fields_ = [("sv", C.c_void_p), ("dQ", C.c_void_p), ("D", C.c_void_p), ("whhT8", C.c_void_p),
                 ("whhTs", C.c_void_p), ("wq", C.c_void_p), ("dGxT", C.c_void_p), ("dGhT", C.c_void_p),
-                ("gwq", C.c_void_p), ("gbq", C.c_void_p), ("B", C.c_int), ("S", C.c_int)]
+                ("gwq", C.c_void_p), ("gbq", C.c_void_p), ("B", C.c_int), ("S", C.c_int), ("gq_stride", C.c_int)]
 
 
 def lib():
@@ -138,6 +138,7 @@ def lib():
                          ("st_gru_td", [C.POINTER(TDArgs), vp]),
                          ("st_gru_seq_bwd", [C.POINTER(SeqBwdArgs), vp]),
                          ("st_gru_grad_fixup", [vp, i, vp, vp, vp, vp, vp]),
+                         ("st_gru_qgrad_reduce", [vp, i, i, vp, vp, vp]),
                          ("st_mx_probe", [vp, vp, vp, vp, vp, vp])):
             f = getattr(L, fn)
             f.argtypes = args
@@ -147,6 +148,7 @@ def lib():
         L.st_gru_rollout_lds_bytes.restype = C.c_int
         L.st_gru_rollout_block.restype = C.c_int
         L.st_gru_serve_lds_bytes.restype = C.c_int
+        L.st_gru_seq_bwd_rows.restype = C.c_int
         L.st_abi_gru_serve.argtypes = [C.POINTER(C.c_int), i]
         L.st_abi_gru_serve.restype = C.c_int
         L._gru_bound = True

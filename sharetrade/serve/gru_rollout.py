@@ -307,6 +307,13 @@ def _run_dir(path: str) -> str:
 def checkpoint_kind(path: str) -> Optional[str]:
     """``meta["kind"]`` of a ``.stck`` file or of the newest file of a ``CheckpointManager`` directory, read from
     the archive's header alone (a recurrent checkpoint carries its replay ring); None when there is none."""
+    meta = checkpoint_meta(path)
+    return None if meta is None else meta.get("kind")
+
+
+def checkpoint_meta(path: str) -> Optional[dict]:
+    """The meta dict of a ``.stck`` file or of the newest file of a ``CheckpointManager`` directory, read from the
+    archive's header alone; None when there is none."""
     import json
     import struct
 
@@ -327,7 +334,7 @@ def checkpoint_kind(path: str) -> Optional[str]:
             meta = json.loads(f.read(meta_len).decode() or "{}")
         except ValueError:
             return None
-    return meta.get("kind") if isinstance(meta, dict) else None
+    return meta if isinstance(meta, dict) else None
 
 
 class GruPolicy:

@@ -14,6 +14,10 @@ the session's running return -- when the session's next bar arrives.
   host and launches it, ``step_into`` is the launch alone on preallocated device tensors.
 * :func:`reference_gru_serve` is the same bar in PyTorch on the net arithmetic of ``reference_gru_rollout``: the
   ``torch`` backend and the oracle of the GPU tests.
+* Raw bars: a session opened with ``open_raw`` also owns a feature-state row (``csrc/bar_features.h``), and
+  ``step_raw`` / ``step_raw_into`` take the bar as a client observes it (open, high, low, close, volume, minute of
+  the session): one featurise launch (``csrc/bar_features.hip`` bar_features_sessions_kernel) writes the rows'
+  features and closes, then the unchanged serve launch runs on the same stream.
 * :class:`GruBatcher` collects single requests of many client threads into batches with at most one request per
   session, so a session's bars are applied in submission order.
 """
@@ -31,6 +35,7 @@ import numpy as np
 import torch
 
 from ..data import minute_bars as mb
+from ..ops import bar_features as BF
 from ..ops import gru as G
 from ..utils import rng
 from .gru_rollout import KEY_RANK, TAG_ROLLOUT, GruBarNet, GruPolicy, rounding_points
@@ -177,7 +182,8 @@ class GruSessionServer:
     and is meant to be the only stepper while it runs)."""
 
     def __init__(self, policy: GruPolicy, max_sessions: int, ep_len: int = 390, cost: float = 0.01,
-                 backend: str = "auto"):
+                 backend: str = "auto", bar_day: int = mb.BarParams.day, bar_alpha: float = mb.BarParams.alpha,
+                 bar_beta: float = mb.BarParams.beta):
         if backend not in ("auto", "hip", "torch"):
             raise ValueError(f"backend must be auto/hip/torch, got {backend!r}")
         if backend == "auto":
@@ -188,6 +194,14 @@ class GruSessionServer:
         self.S, self.ep_len, self.cost = int(max_sessions), int(ep_len), float(cost)
         # the torch backend carries h unrounded (float64), as the rollout oracle does within one call
         self.table = new_table(self.S, self.device, torch.float32 if backend == "hip" else torch.float64)
+        # raw-bar sessions: the feature state of a slot (ops.bar_features.STATE_FIELDS) and what the definition
+        # needs beside it (data.ohlcv.FeatureParams: session length, GARCH coefficients)
+        if int(bar_day) < 1:
+            raise ValueError("need bar_day >= 1")
+        self.bar_day, self.bar_alpha, self.bar_beta = int(bar_day), float(bar_alpha), float(bar_beta)
+        self.fstate = torch.zeros(self.S, BF.NSTATE, dtype=torch.float32, device=self.device)
+        self._raw = np.zeros(self.S, dtype=bool)
+        self._raw_feat = self._raw_close = None
         self._open = np.zeros(self.S, dtype=bool)
         self._free: List[int] = list(range(self.S - 1, -1, -1))   # pop() hands out the lowest slot first
         self._lock = threading.Lock()   # one weight set per launch; the free list
@@ -238,11 +252,38 @@ class GruSessionServer:
             self._open[slots] = True
         return slots
 
+    def open_raw(self, n: int, sigma, vol_scale, draw_ids: Optional[Sequence[int]] = None) -> List[int]:
+        """:meth:`open` for sessions fed raw bars: also zeroes the slots' feature-state rows and sets their
+        ``sigma`` and ``vol_scale`` (a scalar for all, or one per session; ``data.ohlcv.fit_feature_params``)."""
+        n = int(n)
+        sg = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (n,))
+        vs = np.broadcast_to(np.asarray(vol_scale, dtype=np.float32), (n,))
+        if not (np.all(np.isfinite(sg)) and np.all(sg > 0) and np.all(np.isfinite(vs)) and np.all(vs > 0)):
+            raise ValueError("sigma and vol_scale must be positive")
+        slots = self.open(n, draw_ids)
+        row = np.zeros((n, BF.NSTATE), np.float32)
+        row[:, BF.STATE_COL["sigma"]], row[:, BF.STATE_COL["vol_scale"]] = sg, vs
+        with self._lock:
+            idx = torch.tensor(slots, dtype=torch.long, device=self.device)
+            self.fstate[idx] = torch.from_numpy(row).to(self.device)
+            if self.device.type == "cuda":
+                torch.cuda.current_stream(self.device).synchronize()
+            self._raw[slots] = True
+        return slots
+
+    def is_raw(self, slot: int) -> bool:
+        return self.is_open(slot) and bool(self._raw[int(slot)])
+
+    def _check_raw(self, s: np.ndarray) -> None:
+        if not bool(self._raw[s].all()):
+            raise ValueError(f"session {int(s[~self._raw[s]][0])} was opened without raw-bar state (open_raw)")
+
     def close(self, slots: Union[int, Sequence[int]]) -> None:
         s = self._host_slots(slots)
         with self._lock:
             self._check_open(s)
             self._open[s] = False
+            self._raw[s] = False
             self._free.extend(int(v) for v in s[::-1])
 
     def _host_slots(self, slots) -> np.ndarray:
@@ -337,6 +378,102 @@ class GruSessionServer:
                 return
             self._launch(B, slots, feat, close, flags, actions, position, reward, q, epsilon, grid)
 
+    # ---------------------------------------------------------------- stepping on raw bars
+    def step_raw(self, slots: ArrayLike, ohlcv: ArrayLike, minute: ArrayLike,
+                 new_episode: Optional[ArrayLike] = None, greedy: bool = True, epsilon: Optional[float] = None,
+                 return_q: bool = False, grid: int = 0) -> GruDecision:
+        """:meth:`step` on bars as a client observes them: ``ohlcv`` [B, 5] (open, high, low, close, volume) and
+        ``minute`` [B] (the bar's index within its session, 0 .. bar_day - 1).  Also raises ``ValueError`` before
+        anything is launched for a session that was opened without raw-bar state, a non-positive price or a
+        minute out of range."""
+        s = self._host_slots(slots)
+        with self._lock:
+            self._check_open(s)
+            self._check_raw(s)
+        B, dev = int(s.size), self.device
+        x = torch.as_tensor(ohlcv).detach().to("cpu", torch.float32).reshape(-1, 5)
+        m = torch.as_tensor(minute).detach().to("cpu").reshape(-1).to(torch.int32)
+        if x.shape[0] != B or m.numel() != B:
+            raise ValueError("one bar [5] and one minute per slot")
+        if not bool(torch.isfinite(x).all()) or bool((x[:, :4] <= 0).any()) or bool((x[:, 4] < 0).any()):
+            raise ValueError("a bar needs finite values, positive prices and a non-negative volume")
+        if bool((m < 0).any()) or bool((m >= self.bar_day).any()):
+            raise ValueError(f"minute outside 0 .. {self.bar_day - 1}")
+        fl = None
+        if new_episode is not None:
+            fl = torch.as_tensor(new_episode).reshape(-1).to(torch.uint8).to(dev).contiguous()
+            if fl.numel() != B:
+                raise ValueError("one new_episode flag per slot")
+        out = GruDecision(actions=torch.empty(B, dtype=torch.int8, device=dev),
+                          position=torch.empty(B, dtype=torch.int32, device=dev),
+                          reward=torch.empty(B, dtype=torch.float32, device=dev),
+                          q=torch.empty(B, 3, dtype=torch.float32, device=dev) if return_q else None)
+        self.step_raw_into(torch.from_numpy(s.astype(np.int32)).to(dev), x.to(dev).contiguous(),
+                           m.to(dev).contiguous(), fl, out.actions, out.position, out.reward, out.q,
+                           epsilon=self._eps(greedy, epsilon), grid=grid)
+        return out
+
+    def step_raw_into(self, slots: torch.Tensor, ohlcv: torch.Tensor, minute: torch.Tensor,
+                      flags: Optional[torch.Tensor], actions: torch.Tensor, position: torch.Tensor,
+                      reward: torch.Tensor, q: Optional[torch.Tensor] = None, *, epsilon: float = math.inf,
+                      grid: int = 0, feat: Optional[torch.Tensor] = None,
+                      close: Optional[torch.Tensor] = None) -> None:
+        """:meth:`step_into` on raw bars: the featurise launch, then the serve launch, on the current stream; no
+        host check, no sync.  ``ohlcv`` fp32 [B, 5], ``minute`` int32 [B]; the caller guarantees that the slots
+        other than -1 are open raw sessions.  ``feat`` bf16 [>= B, 8] and ``close`` fp32 [>= B] receive the rows
+        the serve launch reads (default: the server's own scratch, grown when a larger batch comes)."""
+        B = int(slots.shape[0])
+        if B < 1:
+            raise ValueError("an empty batch")
+        for name, t, dt, k in (("slots", slots, torch.int32, 1), ("ohlcv", ohlcv, torch.float32, 5),
+                               ("minute", minute, torch.int32, 1)):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.numel() < B * k:
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of at least {B * k} values on "
+                                 f"{self.device}")
+        if feat is None or close is None:
+            if self._raw_feat is None or self._raw_feat.shape[0] < B:
+                self._raw_feat = torch.zeros(B, mb.NFEAT, dtype=torch.bfloat16, device=self.device)
+                self._raw_close = torch.zeros(B, dtype=torch.float32, device=self.device)
+            feat, close = self._raw_feat, self._raw_close
+        if (feat.dtype != torch.bfloat16 or close.dtype != torch.float32 or feat.device != self.device
+                or close.device != self.device or not feat.is_contiguous() or not close.is_contiguous()
+                or feat.numel() < B * mb.NFEAT or close.numel() < B):
+            raise ValueError("feat must be bf16 [>= B, 8] and close fp32 [>= B], contiguous, on the server's device")
+        if self.backend == "torch":
+            self._featurise_torch(B, slots, ohlcv, minute, feat, close)
+        else:
+            from ..ops import native
+
+            a = BF.BarSessionsArgs(slots.data_ptr(), ohlcv.data_ptr(), minute.data_ptr(), self.fstate.data_ptr(),
+                                   feat.data_ptr(), close.data_ptr(), B, self.S, self.bar_day, self.bar_alpha,
+                                   self.bar_beta)
+            with torch.cuda.device(self.device):
+                native.check(BF.lib().st_bar_features_sessions(C.byref(a), native.stream_handle()),
+                             "st_bar_features_sessions")
+        self.step_into(slots, feat.view(-1, mb.NFEAT)[:B], close.view(-1)[:B], flags, actions, position, reward, q,
+                       epsilon=epsilon, grid=grid)
+
+    def _featurise_torch(self, B, slots, ohlcv, minute, feat, close) -> None:
+        """The featurise launch on the host: ``data.ohlcv.featurise_numpy`` on one bar per valid row."""
+        from ..data import ohlcv as ov
+
+        sl = slots[:B].long()
+        ok = (sl >= 0) & (sl < self.S)
+        idx = sl[ok]
+        if int(idx.numel()) == 0:
+            return
+        st = self.fstate[idx].cpu().numpy()
+        x = ohlcv.view(-1, 5)[:B][ok].cpu().numpy()
+        bars = ov.Bars(*(np.ascontiguousarray(x[:, k:k + 1]) for k in range(5)),
+                       minute=minute[:B][ok].cpu().numpy().astype(np.int64)[:, None])
+        fp = ov.FeatureParams(self.bar_day, self.bar_alpha, self.bar_beta, st[:, BF.STATE_COL["sigma"]],
+                              st[:, BF.STATE_COL["vol_scale"]])
+        r = ov.featurise_numpy(bars, fp, state=st)
+        self.fstate[idx] = torch.from_numpy(r.state).to(self.device)
+        okc = ok.to(feat.device)
+        feat.view(-1, mb.NFEAT)[:B][okc] = torch.from_numpy(r.feat[:, 0]).to(torch.bfloat16).to(feat.device)
+        close.view(-1)[:B][okc] = torch.from_numpy(r.close[:, 0]).to(close.device)
+
     def _launch(self, B, slots, feat, close, flags, actions, position, reward, q, epsilon, grid) -> None:
         from ..ops import native
 
@@ -368,7 +505,8 @@ class GruBatcher:
         self.max_batch = int(max_batch)
         self.max_delay = float(max_delay_us) * 1e-6
         self._cv = threading.Condition()
-        self._q: List[Tuple[int, np.ndarray, float, bool, Future]] = []
+        # (slot, features [8] | ohlcv [5], close | minute, new_episode, future, raw)
+        self._q: List[Tuple[int, np.ndarray, float, bool, Future, bool]] = []
         self._stop = False
         self.batch_sizes: List[int] = []
         self._native = server.backend == "hip"
@@ -379,6 +517,8 @@ class GruBatcher:
                        "feat": torch.empty(n, mb.NFEAT, dtype=torch.bfloat16, **pin),
                        "close": torch.empty(n, dtype=torch.float32, **pin),
                        "flags": torch.empty(n, dtype=torch.uint8, **pin),
+                       "ohlcv": torch.empty(n, 5, dtype=torch.float32, **pin),
+                       "minute": torch.empty(n, dtype=torch.int32, **pin),
                        "act": torch.empty(n, dtype=torch.int8, **pin),
                        "pos": torch.empty(n, dtype=torch.int32, **pin),
                        "rew": torch.empty(n, dtype=torch.float32, **pin)}
@@ -398,7 +538,30 @@ class GruBatcher:
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
-            self._q.append((int(slot), row, float(close), bool(new_episode), fut))
+            self._q.append((int(slot), row, float(close), bool(new_episode), fut, False))
+            self._cv.notify()
+        return fut
+
+    def submit_raw(self, slot: int, ohlcv5: ArrayLike, minute: int, new_episode: bool = False) -> Future:
+        """:meth:`submit` of a raw bar (open, high, low, close, volume; ``minute`` of its session) to a session
+        opened with ``open_raw``.  Raw and featurised bars go in separate batches, each session's in order."""
+        row = np.asarray(ohlcv5.float().cpu() if isinstance(ohlcv5, torch.Tensor) else ohlcv5,
+                         dtype=np.float32).reshape(-1)
+        if row.size != 5:
+            raise ValueError(f"a raw bar holds open, high, low, close, volume, got {row.size} values")
+        if not np.all(np.isfinite(row)) or np.any(row[:4] <= 0) or row[4] < 0:
+            raise ValueError("a bar needs finite values, positive prices and a non-negative volume")
+        if not 0 <= int(minute) < self.server.bar_day:
+            raise ValueError(f"minute outside 0 .. {self.server.bar_day - 1}")
+        if not self.server.is_open(slot):
+            raise ValueError(f"session {slot} is not open")
+        if not self.server.is_raw(slot):
+            raise ValueError(f"session {slot} was opened without raw-bar state (open_raw)")
+        fut: Future = Future()
+        with self._cv:
+            if self._stop:
+                raise RuntimeError("batcher is closed")
+            self._q.append((int(slot), row, int(minute), bool(new_episode), fut, True))
             self._cv.notify()
         return fut
 
@@ -426,11 +589,14 @@ class GruBatcher:
                 if left <= 0:
                     break
                 self._cv.wait(left)
-            # the first request of each session, in order; a session's later requests wait (in order)
+            # the first request of each session, in order; a session's later requests wait (in order); a batch
+            # holds bars of one kind (the first request's), and a session with a deferred bar defers its later ones
             batch, rest, seen = [], [], set()
+            raw = self._q[0][5]
             for item in self._q:
-                if item[0] in seen or len(batch) >= self.max_batch:
+                if item[0] in seen or len(batch) >= self.max_batch or item[5] != raw:
                     rest.append(item)
+                    seen.add(item[0])
                 else:
                     seen.add(item[0])
                     batch.append(item)
@@ -455,10 +621,12 @@ class GruBatcher:
     def _run(self, batch):
         n = len(batch)
         slots = np.asarray([b[0] for b in batch], dtype=np.int32)
-        F = torch.from_numpy(np.stack([b[1] for b in batch])).to(torch.bfloat16)
-        c = np.asarray([b[2] for b in batch], dtype=np.float32)
         fl = np.asarray([b[3] for b in batch], dtype=np.uint8)
         srv = self.server
+        if batch[0][5]:
+            return self._run_raw(batch, n, slots, fl)
+        F = torch.from_numpy(np.stack([b[1] for b in batch])).to(torch.bfloat16)
+        c = np.asarray([b[2] for b in batch], dtype=np.float32)
         if not self._native:
             d = srv.step(slots, F, c, new_episode=fl)
             return d.actions.cpu().numpy(), d.position.cpu().numpy(), d.reward.cpu().numpy()
@@ -473,6 +641,31 @@ class GruBatcher:
             for k in ("slot", "feat", "close", "flags"):
                 d[k][:n].copy_(h[k][:n], non_blocking=True)
             srv.step_into(d["slot"][:n], d["feat"][:n], d["close"][:n], d["flags"][:n], d["act"], d["pos"], d["rew"])
+            for k in ("act", "pos", "rew"):
+                h[k][:n].copy_(d[k][:n], non_blocking=True)
+        self._stream.synchronize()
+        return h["act"][:n].numpy().copy(), h["pos"][:n].numpy().copy(), h["rew"][:n].numpy().copy()
+
+    def _run_raw(self, batch, n, slots, fl):
+        x = np.stack([b[1] for b in batch]).astype(np.float32)
+        m = np.asarray([b[2] for b in batch], dtype=np.int32)
+        srv = self.server
+        if not self._native:
+            d = srv.step_raw(slots, x, m, new_episode=fl)
+            return d.actions.cpu().numpy(), d.position.cpu().numpy(), d.reward.cpu().numpy()
+        with srv._lock:
+            srv._check_open(slots.astype(np.int64))   # a session closed since its submit fails the batch
+            srv._check_raw(slots.astype(np.int64))
+        h, d = self._h, self._d
+        h["slot"][:n].numpy()[:] = slots
+        h["ohlcv"][:n].numpy()[:] = x
+        h["minute"][:n].numpy()[:] = m
+        h["flags"][:n].numpy()[:] = fl
+        with torch.cuda.stream(self._stream):
+            for k in ("slot", "ohlcv", "minute", "flags"):
+                d[k][:n].copy_(h[k][:n], non_blocking=True)
+            srv.step_raw_into(d["slot"][:n], d["ohlcv"][:n], d["minute"][:n], d["flags"][:n], d["act"], d["pos"],
+                              d["rew"], feat=d["feat"], close=d["close"])
             for k in ("act", "pos", "rew"):
                 h[k][:n].copy_(d[k][:n], non_blocking=True)
         self._stream.synchronize()

@@ -226,6 +226,22 @@ class BarReq(BaseModel):
     new_episode: bool = False
 
 
+class OpenReq(BaseModel):
+    raw: bool = False
+    sigma: Optional[float] = None
+    vol_scale: Optional[float] = None
+
+
+class OhlcvReq(BaseModel):
+    open: float
+    high: float
+    low: float
+    close: float
+    volume: float
+    minute: int
+    new_episode: bool = False
+
+
 def make_gru_app(server, batcher=None):
     """The session routes of a :class:`~sharetrade.serve.gru_serve.GruSessionServer`; bars go through
     ``batcher`` (a :class:`~sharetrade.serve.gru_serve.GruBatcher`) when there is one."""
@@ -252,14 +268,40 @@ def make_gru_app(server, batcher=None):
             raise HTTPException(404, f"no open session {sid}")
 
     @app.post("/session")
-    def open_session():
+    def open_session(req: Optional[OpenReq] = None):
+        raw = req is not None and req.raw
+        if raw and (req.sigma is None or req.vol_scale is None):
+            m_err.labels("open").inc()
+            raise HTTPException(400, "a raw session needs sigma and vol_scale")
         try:
-            sid = server.open(1)[0]
+            sid = server.open_raw(1, req.sigma, req.vol_scale)[0] if raw else server.open(1)[0]
+        except ValueError as e:
+            m_err.labels("open").inc()
+            raise HTTPException(400, str(e))
         except RuntimeError as e:
             m_err.labels("open").inc()
             raise HTTPException(503, str(e))
         m_open.inc()
-        return {"session": int(sid)}
+        return {"session": int(sid), "raw": True} if raw else {"session": int(sid)}
+
+    @app.post("/session/{sid}/ohlcv")
+    async def ohlcv_bar(sid: int, req: OhlcvReq):
+        """One bar as the client observes it; the session must have been opened with ``"raw": true``."""
+        t0 = time.perf_counter()
+        _known(sid, "ohlcv")
+        row = [req.open, req.high, req.low, req.close, req.volume]
+        try:
+            if batcher is not None:
+                a, pos, rew = await asyncio.wrap_future(batcher.submit_raw(sid, row, req.minute, req.new_episode))
+            else:
+                d = await asyncio.to_thread(server.step_raw, [sid], [row], [req.minute], [req.new_episode])
+                a, pos, rew = int(d.actions.cpu()[0]), int(d.position.cpu()[0]), float(d.reward.cpu()[0])
+        except ValueError as e:
+            m_err.labels("ohlcv").inc()
+            raise HTTPException(409, str(e))
+        m_bars.inc()
+        m_lat.observe(time.perf_counter() - t0)
+        return {"action": repr(action_of(a)), "index": int(a), "position": int(pos), "reward": float(rew)}
 
     @app.post("/session/{sid}/bar")
     async def bar(sid: int, req: BarReq):

@@ -54,7 +54,8 @@ class RecurrentDQN:
                  replay_segments: int = 1 << 17, bars: int = 4096, ep_len: int = 390, burn_in: int = 4,
                  target_every: int = 100, cost: float = 0.01, lr: float = 3e-4, seed: Optional[int] = None,
                  bar_params: Optional[mb.BarParams] = None, actor_grid: int = 0, grad_sync=None,
-                 overlap_act: bool = False, actor_kernel: str = "auto", world_size: int = 1):
+                 overlap_act: bool = False, actor_kernel: str = "auto", world_size: int = 1, bank=None,
+                 deterministic: bool = False):
         if device.type != "cuda":
             raise ValueError("RecurrentDQN runs on the GPU (MX-fp8 / bf16 MFMA kernels)")
         if envs % G.RN:
@@ -85,6 +86,12 @@ class RecurrentDQN:
         # so the sum is the mean over the global batch (B x world_size segments)
         self.grad_sync = grad_sync
         self.world_size = int(world_size)
+        # deterministic: an update whose parameters do not depend on the order in which workgroups arrive -- the
+        # weight-gradient GEMMs without split-K (no atomic accumulation) and the Q-head gradient as per-workgroup
+        # rows summed in order (GruSeqBwd::gq_stride) instead of atomics onto one row.  Two learners of one seed
+        # then train bit-equal parameters; the default keeps the faster atomic sums (equal to reduction-order
+        # noise).  The loss statistic stays an atomic sum either way.
+        self.deterministic = bool(deterministic)
         # capture_sync: the backend's collectives can be captured (RCCL): the all-reduce stays inside the
         # update graph, on the main stream while the overlapped actor still runs on its side stream
         self.capture_sync = False
@@ -148,8 +155,21 @@ class RecurrentDQN:
         self.pk["on1"] = {k: torch.zeros_like(v) for k, v in self.pk["on"].items()}
         self._par = 0
         # ---------------------------------------------------------------- data + envs
+        # bank: (close fp32 [envs, bars], feat bf16 [envs, bars, 8]) on the device, e.g. windows of real bars
+        # (data.ohlcv.window_bank); default: the synthetic generator's bars of this seed
         self.bp = bar_params or mb.BarParams()
-        self.close, self.feat = mb.generate_gpu(self.E, self.T, dev, self.bp, seed=self.seed)
+        self.external_bank = bank is not None
+        if bank is None:
+            self.close, self.feat = mb.generate_gpu(self.E, self.T, dev, self.bp, seed=self.seed)
+        else:
+            close, feat = bank
+            for name, t, dt, shp in (("close", close, f32, (self.E, self.T)),
+                                     ("feat", feat, b16, (self.E, self.T, mb.NFEAT))):
+                same_dev = isinstance(t, torch.Tensor) and t.device.type == dev.type and \
+                    (dev.index is None or t.device.index == dev.index)
+                if not same_dev or t.dtype != dt or tuple(t.shape) != shp or not t.is_contiguous():
+                    raise ValueError(f"bank {name} must be a contiguous {dt} tensor of shape {shp} on {dev}")
+            self.close, self.feat = close, feat
         self.ret = mb.bar_returns(self.close)
         g = np.random.default_rng(self.seed)
         start = torch.from_numpy(g.integers(0, self.T - self.ep_len - 1, size=self.E).astype(np.int32)).to(dev)
@@ -286,7 +306,14 @@ class RecurrentDQN:
             bw.whhT8, bw.whhTs = self._on(par)["whhT8"].data_ptr(), self._on(par)["whhTs"].data_ptr()
             bw.dGxT, bw.dGhT = self.dGxT.data_ptr(), self.dGhT.data_ptr()
             bw.gwq, bw.gbq = self.dP["w_q"].data_ptr(), self.dP["b_q"].data_ptr()
-            bw.B, bw.S = self.B, self.S
+            bw.B, bw.S, bw.gq_stride = self.B, self.S, 0
+            if self.deterministic:
+                if not hasattr(self, "gq_part"):
+                    self.gq_rows = self.B // int(self.k.st_gru_seq_bwd_rows())
+                    self.gq_part = torch.zeros(self.gq_rows, 3 * HID + 4, device=self.dev)
+                bw.gwq = self.gq_part.data_ptr()
+                bw.gbq = self.gq_part.data_ptr() + 3 * HID * 4
+                bw.gq_stride = int(self.gq_part.stride(0))
             self._bwds.append(bw)
         ag = self.cfg.agent
         op = native.OptimParams()
@@ -357,11 +384,18 @@ class RecurrentDQN:
         self.loss.zero_()
         native.check(k.st_gru_td(self._td, sh), "st_gru_td")
         self.gflat.zero_()
+        if self.deterministic:
+            self.gq_part.zero_()
         native.check(k.st_gru_seq_bwd(self._bwds[self._par], sh), "st_gru_seq_bwd")
+        if self.deterministic:
+            native.check(k.st_gru_qgrad_reduce(self.gq_part.data_ptr(), self.gq_rows, int(self.gq_part.stride(0)),
+                                               self.dP["w_q"].data_ptr(), self.dP["b_q"].data_ptr(), sh),
+                         "st_gru_qgrad_reduce")
+        sk = 1 if self.deterministic else "auto"
         native.check(kd.st_transpose_bf16(self.X.data_ptr(), XL, self.XT.data_ptr(), R1, RS, XL, sh), "T X")
         # weight gradients; the ones row of HT / ones column RF of X give the bias gradients for free
-        gm.gemm_nt(self.dGhT, self.HT[:, :RS], self.dWhh_ext, gm.EPI_F32, splitk="auto")
-        gm.gemm_nt(self.dGxT, self.XT[:, :RS], self.dP["w_ih"], gm.EPI_F32, accumulate=True, splitk="auto")
+        gm.gemm_nt(self.dGhT, self.HT[:, :RS], self.dWhh_ext, gm.EPI_F32, splitk=sk)
+        gm.gemm_nt(self.dGxT, self.XT[:, :RS], self.dP["w_ih"], gm.EPI_F32, accumulate=True, splitk=sk)
         native.check(k.st_gru_grad_fixup(self.dWhh_ext.data_ptr(), HID + 64, self.dP["w_hh"].data_ptr(),
                                          self.dP["b_hh"].data_ptr(), self.dP["w_ih"].data_ptr(),
                                          self.dP["b_ih"].data_ptr(), sh), "grad fixup")
@@ -544,6 +578,9 @@ class RecurrentDQN:
         from ..serve.gru_rollout import GruPolicy
 
         pol = GruPolicy.from_learner(self, net=net)
+        if (close is None or feat is None) and self.external_bank:
+            raise ValueError("this learner trains on an external bank: backtest() needs the held-out close and feat "
+                             "(the synthetic generator's bars are not its data)")
         if close is None:
             T = 4 * self.ep_len + 1 if bars is None else int(bars)
             close, feat = mb.generate_gpu(int(envs), T, self.dev, self.bp, seed=self.seed + 1000)

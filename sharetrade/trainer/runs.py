@@ -74,10 +74,13 @@ def run(kind: str, cfg: Config, iterations: int, device: Optional[torch.device] 
         ckpt_every: int = 0, resume: bool = False, graph: bool = True, learner=None, ctx=None,
         bucket_mb: float = 64.0, capture_sync: bool = True, layer_overlap: bool = True,
         trace_path: Optional[str] = None, on_step=None, final_dir: Optional[str] = None,
-        **learner_kw) -> Dict[str, Any]:
+        extra_meta: Optional[Dict[str, Any]] = None, **learner_kw) -> Dict[str, Any]:
     """Run ``iterations`` act + update iterations (counting any restored ones); returns final stats.
     ``on_step(i)`` runs before every iteration (``--elastic``: fault injection + heartbeat progress);
-    ``final_dir``: each rank writes its final learner state there (``final-rank-<r>.stck``)."""
+    ``final_dir``: each rank writes its final learner state there (``final-rank-<r>.stck``).  ``extra_meta`` goes
+    into every checkpoint's meta; its ``bar_features`` entry (a run on a bars file: ``data.ohlcv``) names the file's
+    CRC32C, and a resume from a checkpoint of another file is refused (the bars are not in the checkpoint)."""
+    extra_meta = dict(extra_meta or {})
     dp = ctx is not None and ctx.is_distributed
     dev = device or (ctx.device if ctx is not None else torch.device("cuda", 0))
     if dp:
@@ -120,6 +123,10 @@ def run(kind: str, cfg: Config, iterations: int, device: Optional[torch.device] 
             st, meta = load_ckpt(path)
             if meta.get("kind") != kind:
                 raise ValueError(f"checkpoint is a {meta.get('kind')!r} run, not {kind!r}")
+            want, have = extra_meta.get("bar_features"), meta.get("bar_features")
+            if (want or have) and (want or {}).get("crc32c") != (have or {}).get("crc32c"):
+                raise ValueError(f"{path} was trained on bars with CRC32C {(have or {}).get('crc32c')}, this run's "
+                                 f"bars have {(want or {}).get('crc32c')}: the bars are not in the checkpoint")
             d.load_state_dict(st)
             done = int(meta["step"])
     ml = MetricsLogger(metrics_path)
@@ -147,7 +154,7 @@ def run(kind: str, cfg: Config, iterations: int, device: Optional[torch.device] 
         one()
         if mgr is not None and mgr.should_save(done):
             _sync(dev)
-            mgr.save(done, d.state_dict(), {"kind": kind, "config": cfg.to_dict()})
+            mgr.save(done, d.state_dict(), {"kind": kind, "config": cfg.to_dict(), **extra_meta})
         if log_every and done % log_every == 0:
             _sync(dev)
             now = time.perf_counter()
