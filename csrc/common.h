@@ -44,6 +44,14 @@ ST_DEV f4v mfma16(s4v a, s4v b, f4v c) { return __builtin_amdgcn_mfma_f32_16x16x
 
 ST_DEV f4v zero4() { f4v z = {0.f, 0.f, 0.f, 0.f}; return z; }
 
+// ----------------------------------------------------------------- LDS-only workgroup barrier
+// s_waitcnt lgkmcnt(0) only (gfx9 split vmcnt field left at its maximum), then the barrier: LDS traffic is
+// ordered, global loads / stores and LDS-DMA stay in flight (a __syncthreads() drains them: vmcnt(0))
+ST_DEV void lds_barrier() {
+  __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4));
+  asm volatile("s_barrier" ::: "memory");
+}
+
 // ----------------------------------------------------------------- Philox4x32-10
 // Bit-identical to sharetrade/utils/rng.py::philox4x32.
 ST_DEV void philox4x32(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {

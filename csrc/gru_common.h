@@ -115,12 +115,6 @@ ST_DEV void gru_q_row(const float* sWq, const float* sQp, int row, float (&q)[3]
   }
 }
 
-// s_waitcnt lgkmcnt(0) only, then the barrier: LDS traffic is ordered, global loads / stores stay in flight
-ST_DEV void lds_barrier() {
-  __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4));
-  asm volatile("s_barrier" ::: "memory");
-}
-
 // the epsilon-greedy draw of the backtest and the server (a served session mirrors a rollout env): counter
 // (c0, c1, 0, "GRB1") under the actors' key; `a` is the greedy action
 constexpr uint32_t TAG_ROLLOUT = 0x47524231u;

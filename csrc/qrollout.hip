@@ -2,7 +2,7 @@
 //
 // For env e and day t = start .. start + steps - 1 the rule is the engine's (csrc/trade_rule.h, oracle
 // sharetrade/serve/rollout.py::reference_rollout): window prices[e, t : t+H] -> features -> the flagship
-// 2x128 bf16 Q-net (224 -> 128 -> 128 -> 16, the forward of csrc/qserve.hip) -> argmax -> epsilon-greedy
+// 2x128 bf16 Q-net (224 -> 128 -> 128 -> 16: csrc/qnet_common.h, shared with qserve.hip) -> argmax -> epsilon-greedy
 // (Philox stream 4, exploit ramp on the day t) -> trade at v = prices[e, t+H].  Only the budget and the
 // shares of the 203 inputs depend on earlier actions, and consecutive windows share H - 1 prices, so a
 // workgroup owns its envs for the whole launch:
@@ -19,19 +19,16 @@
 // workgroup's serial chain under the other's MFMA phases.
 #include <type_traits>
 
-#include "common.h"
-#include "trade_rule.h"
+#include "qnet_common.h"
 
 namespace st {
 namespace rollout {
+using namespace qnet;   // padded dims, q_head_row; the kernel includes qnet_weights.h, qnet_layers.h, qnet_head.h
 
-constexpr int INP = 224, HP = 128;              // padded dims of the flagship layout (models/qnet.py)
 constexpr int C = 32;                           // envs per workgroup
 constexpr int NW = 4, NT = 64 * NW;
 constexpr int NET = C / 16;                     // 16-env tiles per workgroup
 constexpr int MT = HP / (16 * NW);              // 16-unit m-tiles per wave
-constexpr int KS0 = INP / 32, KS1 = HP / 32;
-constexpr int SX = INP + 16, SH = HP + 16;      // activation row strides (bf16)
 constexpr int D = 32;                           // days per price block
 constexpr int RING = 256, SP = RING + 1;        // price ring per env (floats), padded row stride
 constexpr int RPW = C / NW;                     // feature rows per wave
@@ -47,13 +44,8 @@ constexpr int OFF_FS = OFF_FB + C * 4;              // fp32 [C] shares feature o
 constexpr int LDS_BYTES = OFF_FS + C * 4;
 static_assert(OFF_H1 % 16 == 0 && OFF_P % 16 == 0 && OFF_INV % 16 == 0 && OFF_FB % 16 == 0, "16-byte carves");
 
-// s_waitcnt lgkmcnt(0) only: the barriers order LDS traffic and leave the trace stores and the price
-// prefetch in flight (a __syncthreads() drains them: vmcnt(0))
-ST_DEV void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4)); }
-ST_DEV void bar() {
-  wait_lgkm0();
-  asm volatile("s_barrier" ::: "memory");
-}
+// the barriers order LDS traffic and leave the trace stores and the price prefetch in flight
+ST_DEV void bar() { lds_barrier(); }
 
 struct RolloutParams {
   const float* prices;     // [E][ld] fp32, T valid values per row
@@ -93,29 +85,7 @@ __global__ void __launch_bounds__(NT, 2) qrollout_kernel(RolloutParams p) {
   const bool greedy = __builtin_isinf(p.eps);
 
   // ---------------------------------------------------------------- weights -> VGPRs (once)
-  s8v aW0[MT][KS0], aW1[MT][KS1], aW2[KS1];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const bf16_t* w0 = p.wq + p.off_w0 + (size_t)(m0 + 16 * i + l16) * INP + 8 * g4;
-#pragma unroll
-    for (int ks = 0; ks < KS0; ++ks) aW0[i][ks] = *reinterpret_cast<const s8v*>(w0 + ks * 32);
-    const bf16_t* w1 = p.wq + p.off_w1 + (size_t)(m0 + 16 * i + l16) * HP + 8 * g4;
-#pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) aW1[i][ks] = *reinterpret_cast<const s8v*>(w1 + ks * 32);
-  }
-  {
-    const bf16_t* w2 = p.wq + p.off_w2 + (size_t)l16 * HP + 8 * g4;
-#pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) aW2[ks] = *reinterpret_cast<const s8v*>(w2 + ks * 32);
-  }
-  float bb[MT][4];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bb[i][j] = p.wf[p.off_b1 + m0 + 16 * i + 4 * g4 + j];
-  float b2[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) b2[j] = p.wf[p.off_b2 + j];
+#include "qnet_weights.h"
 
   const int tend = p.start + p.steps;
   const int ntiles = (p.E + C - 1) / C;
@@ -226,74 +196,14 @@ __global__ void __launch_bounds__(NT, 2) qrollout_kernel(RolloutParams p) {
         if (mode) p0(std::integral_constant<int, 1>{});
         else p0(std::integral_constant<int, 0>{});
         bar();
-        // ---------------------------------------------------------- P1: layer 1
-        {
-          f4v acc[MT][NET];
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int n = 0; n < NET; ++n) acc[i][n] = zero4();
-#pragma unroll
-          for (int ks = 0; ks < KS0; ++ks) {
-            s8v bf[NET];
-#pragma unroll
-            for (int n = 0; n < NET; ++n) bf[n] = lds_ld8(sX + (16 * n + l16) * SX + ks * 32 + 8 * g4);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-              for (int n = 0; n < NET; ++n) acc[i][n] = mfma32(aW0[i][ks], bf[n], acc[i][n]);
-          }
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int n = 0; n < NET; ++n) {
-              const f4v v = acc[i][n];
-              lds_st4(sH1 + (16 * n + l16) * SH + m0 + 16 * i + 4 * g4, fmaxf(v[0], 0.f), fmaxf(v[1], 0.f),
-                      fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
-            }
-        }
-        bar();
-        // ---------------------------------------------------------- P2: layer 2 (+ b1) -> H2 (over X)
-        {
-          f4v acc[MT][NET];
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int n = 0; n < NET; ++n) acc[i][n] = zero4();
-#pragma unroll
-          for (int ks = 0; ks < KS1; ++ks) {
-            s8v bf[NET];
-#pragma unroll
-            for (int n = 0; n < NET; ++n) bf[n] = lds_ld8(sH1 + (16 * n + l16) * SH + ks * 32 + 8 * g4);
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-              for (int n = 0; n < NET; ++n) acc[i][n] = mfma32(aW1[i][ks], bf[n], acc[i][n]);
-          }
-#pragma unroll
-          for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int n = 0; n < NET; ++n) {
-              const f4v v = acc[i][n];
-              lds_st4(sH2 + (16 * n + l16) * SH + m0 + 16 * i + 4 * g4, fmaxf(v[0] + bb[i][0], 0.f),
-                      fmaxf(v[1] + bb[i][1], 0.f), fmaxf(v[2] + bb[i][2], 0.f), fmaxf(v[3] + bb[i][3], 0.f));
-            }
-        }
-        bar();
+        // ---------------------------------------------------------- P1, P2: layers 1 and 2 -> H2 (over X)
+#include "qnet_layers.h"
         // ---------------------------------------------------------- P3: output, policy, trade
         if (wave < NET) {
-          f4v acc = zero4();   // wave w: 16-env tile w; lanes g4 == 0 end up with q[0..3] of env 16 w + l16
-#pragma unroll
-          for (int ks = 0; ks < KS1; ++ks)
-            acc = mfma32(aW2[ks], lds_ld8(sH2 + (16 * wave + l16) * SH + ks * 32 + 8 * g4), acc);
+#include "qnet_head.h"   // wave w: 16-env tile w; lanes g4 == 0 end up with the outputs of env 16 w + l16 in acc
           if (g4 == 0) {
             float q[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-              q[j] = acc[j] + b2[j];
-              if (p.output_relu) q[j] = fmaxf(q[j], 0.f);
-            }
-            int a = argmax3(q[0], q[1], q[2]);
+            int a = q_head_row(acc, b2, p.output_relu, q);
             if (!greedy) {
               float u1, u2;
               policy_draw(p.env_offset + (uint32_t)env, (unsigned long long)t, p.key0, p.key1, u1, u2, 4u);

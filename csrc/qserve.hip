@@ -23,27 +23,22 @@
 //    only, so the DMA stays in flight across them.  One workgroup per CU (156 KB of LDS);
 //  * otherwise (any stride): register gather with every load unconditional (clamped indices) and 7
 //    quads x 5 loads in flight per thread; activation tiles only in LDS (49 KB), two workgroups per CU.
-#include "common.h"
-#include "trade_rule.h"
+#include "qnet_common.h"
 
 namespace st {
 namespace serve {
+using namespace qnet;   // padded dims, q_head_row; the kernel includes qnet_weights.h, qnet_layers.h, qnet_head.h
 
-constexpr int INP = 224, HP = 128, OUTP = 16;   // padded dims of the flagship layout (models/qnet.py)
 constexpr int C = 64;                           // request rows per tile
 constexpr int NW = 4, NT = 64 * NW;             // register-gather build (STREAM: 8 waves, see the kernel)
 constexpr int NET = C / 16;                     // 16-row tiles per tile
-constexpr int MT = HP / (16 * NW);              // 16-unit m-tiles per wave (2; STREAM: 1)
-constexpr int KS0 = INP / 32, KS1 = HP / 32;
-constexpr int SX = INP + 16, SH = HP + 16;      // activation row strides (bf16)
 constexpr int MAXLD = 208;                      // STREAM: widest row stride staged (floats)
 constexpr int ACT_BYTES = (C * SX + C * SH) * 2;
 constexpr int RAW_BYTES = 2 * C * MAXLD * 4;    // two row buffers: tile t+1 lands while tile t runs
 constexpr int LDS_BYTES = ACT_BYTES;                                   // register-gather build
 constexpr int LDS_BYTES_STREAM = RAW_BYTES + ACT_BYTES + 2 * C * 4;    // + staged rows, steps, 1/last
 
-// s_waitcnt immediates (gfx9 split vmcnt field): lgkmcnt(0) only / vmcnt(0) only
-ST_DEV void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xF | (0x3 << 14) | (0x7 << 4)); }
+// s_waitcnt vmcnt(0) only (gfx9 split vmcnt field)
 ST_DEV void wait_vm0() { __builtin_amdgcn_s_waitcnt((0x7 << 4) | (0xF << 8)); }
 // global_load_lds_dwordx4 issued from inline asm: with the builtin, hipcc orders every later LDS store
 // behind the DMA (s_waitcnt vmcnt(0) at the first ds_write after it: the MFMA phases' epilogues), which
@@ -75,7 +70,8 @@ __global__ void __launch_bounds__(STREAM ? 512 : 256, STREAM ? 1 : 2) qserve_ker
   // STREAM: one workgroup per CU (156 KB of LDS) of 8 waves -- two per SIMD, each owning 16 hidden
   // units -- so one wave's MFMAs overlap the other's VALU / LDS work; register gather: 4 waves x 32 units,
   // two workgroups per CU
-  constexpr int NWk = STREAM ? 8 : 4, NTk = 64 * NWk, MTk = HP / (16 * NWk), TPR = NTk / C;
+  constexpr int NWk = STREAM ? 8 : 4, NTk = 64 * NWk, TPR = NTk / C;
+  constexpr int MT = HP / (16 * NWk);   // 16-unit m-tiles per wave: 1 (STREAM) or 2
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* sRaw = reinterpret_cast<float*>(smem);   // STREAM: the tile's raw rows [C][ld]
   bf16_t* sX = reinterpret_cast<bf16_t*>(smem + (STREAM ? RAW_BYTES : 0));   // [C][SX]; H2 [C][SH] later
@@ -84,40 +80,17 @@ __global__ void __launch_bounds__(STREAM ? 512 : 256, STREAM ? 1 : 2) qserve_ker
   float* sInv = sSteps + C;                                                            // STREAM: [C]
   const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m0 = 16 * MTk * wave;
+  const int m0 = 16 * MT * wave;
   const int H = p.H;
 
   // ---------------------------------------------------------------- weights -> VGPRs (once)
-  s8v aW0[MTk][KS0], aW1[MTk][KS1], aW2[KS1];
-#pragma unroll
-  for (int i = 0; i < MTk; ++i) {
-    const bf16_t* w0 = p.wq + p.off_w0 + (size_t)(m0 + 16 * i + l16) * INP + 8 * g4;
-#pragma unroll
-    for (int ks = 0; ks < KS0; ++ks) aW0[i][ks] = *reinterpret_cast<const s8v*>(w0 + ks * 32);
-    const bf16_t* w1 = p.wq + p.off_w1 + (size_t)(m0 + 16 * i + l16) * HP + 8 * g4;
-#pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) aW1[i][ks] = *reinterpret_cast<const s8v*>(w1 + ks * 32);
-  }
-  {
-    const bf16_t* w2 = p.wq + p.off_w2 + (size_t)l16 * HP + 8 * g4;
-#pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) aW2[ks] = *reinterpret_cast<const s8v*>(w2 + ks * 32);
-  }
-  float bb[MTk][4];
-#pragma unroll
-  for (int i = 0; i < MTk; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bb[i][j] = p.wf[p.off_b1 + m0 + 16 * i + 4 * g4 + j];
-  float b2[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) b2[j] = p.wf[p.off_b2 + j];
+#include "qnet_weights.h"
 
   // barrier between phases: STREAM waits for LDS traffic only (a __syncthreads() would also drain the
   // row DMA in flight: vmcnt(0))
   auto bar = [&]() {
     if constexpr (STREAM) {
-      wait_lgkm0();
-      asm volatile("s_barrier" ::: "memory");
+      lds_barrier();
     } else {
       __syncthreads();
     }
@@ -202,6 +175,8 @@ __global__ void __launch_bounds__(STREAM ? 512 : 256, STREAM ? 1 : 2) qserve_ker
             for (int q = 0; q < 4; ++q) {
               const int k = c + q;
               const float w = v[m][q];
+              // feat_price / feat_budget / feat_shares of trade_rule.h, spelled out (shares arrive as fp32; through
+              // the functions the weight prologue is scheduled differently: profiles/qnet_shared_forward.md)
               const float fp = p.feat_mode ? __fsub_rn(__fmul_rn(w, inv), 1.0f) : w;
               const float fb = p.feat_mode ? __fmul_rn(w, p.inv_b0) : w;
               const float fs = p.feat_mode ? __fmul_rn(__fmul_rn(w, last), p.inv_b0) : w;
@@ -213,76 +188,16 @@ __global__ void __launch_bounds__(STREAM ? 512 : 256, STREAM ? 1 : 2) qserve_ker
       }
     }
     bar();
-    // -------------------------------------------------------------- P1: layer 1
-    {
-      f4v acc[MTk][NET];
-#pragma unroll
-      for (int i = 0; i < MTk; ++i)
-#pragma unroll
-        for (int n = 0; n < NET; ++n) acc[i][n] = zero4();
-#pragma unroll
-      for (int ks = 0; ks < KS0; ++ks) {
-        s8v b[NET];
-#pragma unroll
-        for (int n = 0; n < NET; ++n) b[n] = lds_ld8(sX + (16 * n + l16) * SX + ks * 32 + 8 * g4);
-#pragma unroll
-        for (int i = 0; i < MTk; ++i)
-#pragma unroll
-          for (int n = 0; n < NET; ++n) acc[i][n] = mfma32(aW0[i][ks], b[n], acc[i][n]);
-      }
-#pragma unroll
-      for (int i = 0; i < MTk; ++i)
-#pragma unroll
-        for (int n = 0; n < NET; ++n) {
-          const f4v v = acc[i][n];
-          lds_st4(sH1 + (16 * n + l16) * SH + m0 + 16 * i + 4 * g4, fmaxf(v[0], 0.f), fmaxf(v[1], 0.f),
-                  fmaxf(v[2], 0.f), fmaxf(v[3], 0.f));
-        }
-    }
-    bar();
-    // -------------------------------------------------------------- P2: layer 2 (+ b1) -> H2 (over X)
+    // -------------------------------------------------------------- P1, P2: layers 1 and 2 -> H2 (over X)
     bf16_t* sH2 = sX;
-    {
-      f4v acc[MTk][NET];
-#pragma unroll
-      for (int i = 0; i < MTk; ++i)
-#pragma unroll
-        for (int n = 0; n < NET; ++n) acc[i][n] = zero4();
-#pragma unroll
-      for (int ks = 0; ks < KS1; ++ks) {
-        s8v b[NET];
-#pragma unroll
-        for (int n = 0; n < NET; ++n) b[n] = lds_ld8(sH1 + (16 * n + l16) * SH + ks * 32 + 8 * g4);
-#pragma unroll
-        for (int i = 0; i < MTk; ++i)
-#pragma unroll
-          for (int n = 0; n < NET; ++n) acc[i][n] = mfma32(aW1[i][ks], b[n], acc[i][n]);
-      }
-#pragma unroll
-      for (int i = 0; i < MTk; ++i)
-#pragma unroll
-        for (int n = 0; n < NET; ++n) {
-          const f4v v = acc[i][n];
-          lds_st4(sH2 + (16 * n + l16) * SH + m0 + 16 * i + 4 * g4, fmaxf(v[0] + bb[i][0], 0.f),
-                  fmaxf(v[1] + bb[i][1], 0.f), fmaxf(v[2] + bb[i][2], 0.f), fmaxf(v[3] + bb[i][3], 0.f));
-        }
-    }
-    bar();
+#include "qnet_layers.h"
     // -------------------------------------------------------------- P3: output, argmax, epsilon-greedy
     if (wave < NET) {
-      f4v acc = zero4();   // wave w: 16-row tile w; lanes g4 == 0 end up with q[0..3] of row 16w + l16
-#pragma unroll
-      for (int ks = 0; ks < KS1; ++ks)
-        acc = mfma32(aW2[ks], lds_ld8(sH2 + (16 * wave + l16) * SH + ks * 32 + 8 * g4), acc);
+#include "qnet_head.h"   // wave w: 16-row tile w; lanes g4 == 0 end up with the outputs of row 16 w + l16 in acc
       const int row = r0 + 16 * wave + l16;
       if (g4 == 0 && row < p.B) {
         float q[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          q[j] = acc[j] + b2[j];
-          if (p.output_relu) q[j] = fmaxf(q[j], 0.f);
-        }
-        int a = argmax3(q[0], q[1], q[2]);
+        int a = q_head_row(acc, b2, p.output_relu, q);
         if (p.steps != nullptr) {
           float u1, u2;
           policy_draw((uint32_t)row, p.seq, p.key0, p.key1, u1, u2, 2u);   // (stream 2: the serving draw)

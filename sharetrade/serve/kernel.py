@@ -58,6 +58,32 @@ def supported(layout: qn.QNetLayout) -> bool:
     return tuple(layout.pdims) == PADDED_DIMS + (qn.OUT_PAD,) and layout.n_layers == 3
 
 
+def fill_net_params(p: C.Structure, kernel: str, layout: qn.QNetLayout, params: torch.Tensor, params_bf: torch.Tensor,
+                    history: int, feat_mode: int, output_relu: bool, budget0: float, key: Tuple[int, int]) -> None:
+    """Check ``(layout, history)`` against the flagship-dims kernels (``csrc/qnet_common.h``) and fill the net
+    fields that :class:`ServeParams` and ``RolloutParams`` share: weights, segment offsets, feature mode, key."""
+    if not supported(layout):
+        raise NotImplementedError(f"{kernel} kernel needs padded dims {PADDED_DIMS}, got {layout.pdims}")
+    if history + 3 > PADDED_DIMS[0] or layout.input_dim != history + 2:
+        raise ValueError(f"history {history} does not fit the {PADDED_DIMS[0]}-wide input")
+    seg = layout.segments
+    p.wq, p.wf, p.H = native.ptr(params_bf), native.ptr(params), int(history)
+    p.off_w0, p.off_w1, p.off_b1 = seg["W0"].offset, seg["W1"].offset, seg["b1"].offset
+    p.off_w2, p.off_b2 = seg["W2"].offset, seg["b2"].offset
+    p.feat_mode, p.output_relu = int(feat_mode), int(bool(output_relu))
+    p.inv_b0 = float(np.float32(1.0 / budget0))
+    p.key0, p.key1 = int(key[0]), int(key[1])
+
+
+def epsilon_greedy(greedy: torch.Tensor, u1, u2, epsilon: float, ramp: float, pos) -> torch.Tensor:
+    """The kernels' selection from the NumPy draws ``(u1, u2)``: ``greedy`` (int64) where ``u1 < min(epsilon, pos /
+    ramp)`` in float32 (``pos``: the step or day, scalar or per row), else the random action ``min(int(3 u2), 2)``."""
+    thr = np.minimum(np.float32(epsilon), np.asarray(pos, dtype=np.float32) * np.float32(1.0 / ramp))
+    exploit = torch.from_numpy(np.asarray(u1 < thr)).to(greedy.device)
+    rnd = torch.from_numpy(np.minimum((u2 * np.float32(3)).astype(np.int64), 2)).to(greedy.device)
+    return torch.where(exploit, greedy, rnd)
+
+
 class ServeKernel:
     """One reusable parameter block for ``st_qserve_launch`` (weights by pointer: the caller keeps
     ``params`` / ``params_bf`` alive and may update them in place between launches)."""
@@ -65,20 +91,9 @@ class ServeKernel:
     def __init__(self, layout: qn.QNetLayout, params: torch.Tensor, params_bf: torch.Tensor, *,
                  history: int, feat_mode: int, output_relu: bool, budget0: float, epsilon: float,
                  ramp: float, key: Tuple[int, int]):
-        if not supported(layout):
-            raise NotImplementedError(f"serving kernel needs padded dims {PADDED_DIMS}, got {layout.pdims}")
-        if history + 3 > PADDED_DIMS[0] or layout.input_dim != history + 2:
-            raise ValueError(f"history {history} does not fit the {PADDED_DIMS[0]}-wide input")
-        seg = layout.segments
         p = ServeParams()
-        p.wq, p.wf = native.ptr(params_bf), native.ptr(params)
-        p.H = int(history)
-        p.off_w0, p.off_w1, p.off_b1 = seg["W0"].offset, seg["W1"].offset, seg["b1"].offset
-        p.off_w2, p.off_b2 = seg["W2"].offset, seg["b2"].offset
-        p.feat_mode, p.output_relu = int(feat_mode), int(bool(output_relu))
-        p.inv_b0 = float(np.float32(1.0 / budget0))
+        fill_net_params(p, "serving", layout, params, params_bf, history, feat_mode, output_relu, budget0, key)
         p.eps, p.inv_ramp = float(epsilon), float(np.float32(1.0 / ramp))
-        p.key0, p.key1 = int(key[0]), int(key[1])
         self.p = p
         self._keep = (params, params_bf)
 
@@ -118,7 +133,4 @@ def reference_select(params: torch.Tensor, layout: qn.QNetLayout, states: torch.
     B = x.shape[0]
     u1, u2 = rng.uniforms(key_seed, 0, np.arange(B, dtype=np.uint32), seq, stream=SERVE_STREAM)
     st = torch.as_tensor(steps, dtype=torch.float32).cpu().numpy()
-    thr = np.minimum(np.float32(epsilon), st.astype(np.float32) * np.float32(1.0 / ramp))
-    exploit = torch.from_numpy(u1 < thr).to(x.device)
-    rnd = torch.from_numpy(np.minimum((u2 * np.float32(3)).astype(np.int64), 2)).to(x.device)
-    return torch.where(exploit, greedy.long(), rnd).to(torch.int32), q
+    return epsilon_greedy(greedy.long(), u1, u2, epsilon, ramp, st).to(torch.int32), q

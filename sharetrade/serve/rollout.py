@@ -25,7 +25,7 @@ from ..env import trading as tr
 from ..models import qnet as qn
 from ..ops import native
 from ..utils import rng
-from .kernel import PADDED_DIMS, supported
+from .kernel import epsilon_greedy, fill_net_params
 
 ROLLOUT_STREAM = 4        # Philox counter word 3 of the backtest draws: (env, day_lo, day_hi, 4)
 
@@ -73,20 +73,9 @@ class RolloutKernel:
     def __init__(self, layout: qn.QNetLayout, params: torch.Tensor, params_bf: torch.Tensor, *,
                  history: int, feat_mode: int, output_relu: bool, budget0: float, shares0: int, compat: bool,
                  epsilon: float, ramp: float, key: Tuple[int, int]):
-        if not supported(layout):
-            raise NotImplementedError(f"rollout kernel needs padded dims {PADDED_DIMS}, got {layout.pdims}")
-        if history + 3 > PADDED_DIMS[0] or layout.input_dim != history + 2:
-            raise ValueError(f"history {history} does not fit the {PADDED_DIMS[0]}-wide input")
-        seg = layout.segments
         p = RolloutParams()
-        p.wq, p.wf = native.ptr(params_bf), native.ptr(params)
-        p.H = int(history)
-        p.off_w0, p.off_w1, p.off_b1 = seg["W0"].offset, seg["W1"].offset, seg["b1"].offset
-        p.off_w2, p.off_b2 = seg["W2"].offset, seg["b2"].offset
-        p.feat_mode, p.output_relu, p.compat_env = int(feat_mode), int(bool(output_relu)), int(bool(compat))
-        p.b0, p.s0 = float(budget0), int(shares0)
-        p.inv_b0 = float(np.float32(1.0 / budget0))
-        p.key0, p.key1 = int(key[0]), int(key[1])
+        fill_net_params(p, "rollout", layout, params, params_bf, history, feat_mode, output_relu, budget0, key)
+        p.compat_env, p.b0, p.s0 = int(bool(compat)), float(budget0), int(shares0)
         self.p = p
         self.epsilon, self.inv_ramp = float(epsilon), float(np.float32(1.0 / ramp))
         self.device = params.device
@@ -182,10 +171,7 @@ def reference_rollout(params: torch.Tensor, layout: qn.QNetLayout, prices: torch
         a = torch.argmax(q, dim=1)   # first max on ties (TF ArgMax)
         if not greedy_policy:
             u1, u2 = rng.uniforms(key_seed, 0, ids, t, stream=ROLLOUT_STREAM)
-            thr = np.minimum(np.float32(epsilon), np.float32(t) * np.float32(1.0 / ramp))
-            exploit = torch.from_numpy(u1 < thr).to(dev)
-            rnd = torch.from_numpy(np.minimum((u2 * np.float32(3)).astype(np.int64), 2)).to(dev)
-            a = torch.where(exploit, a, rnd)
+            a = epsilon_greedy(a, u1, u2, epsilon, ramp, t)
         if forced_actions is not None:
             a = forced_actions[:, i].to(dev).long()
         v = P[:, t + H]
