@@ -1,8 +1,9 @@
 // Fused learner of the GRU(256) recurrent Q-net (BASELINE config 5).
 //
 // Replaces a per-time-step chain of GEMM + elementwise launches (~130 kernels per update)
-// with two persistent kernels; a workgroup owns 32 sampled sequences for all time steps,
-// wave w owns hidden units 32w..32w+31 of all three gates (the actor's tiling, gru.hip):
+// with two persistent kernels; a workgroup owns its sampled sequences (32 in the forward, 16 in the
+// backward) for all time steps, wave w owns hidden units 32w..32w+31 of all three gates (the actor's
+// tiling, gru.hip):
 //
 //   gru_seq_fwd_kernel  (grid B/32 x 2: online and target net in one launch)
 //     S+1 steps of the recurrence on-chip, exactly the actor's arithmetic: W_hh as MX-fp8
@@ -11,14 +12,19 @@
 //     The online net saves r, z, n, gh_n, h_prev (bf16, in the lanes' own accumulator
 //     order -> one 16-byte store / load per quantity and tile) and the masked h rows the
 //     weight-gradient GEMM needs.
-//   gru_seq_bwd_kernel  (grid B/32)
+//   gru_seq_bwd_kernel  (grid B/16: LBB sequences per workgroup, one MFMA env tile; workgroup b reads
+//     tile b & 1 of forward block b >> 1 of the saves)
 //     backward through time: the recurrent gradient dL/dh stays in registers; per step
-//     the fused GRU backward writes dGx / dGh (bf16) and the dGh tile to LDS, then
-//     dh_{t-1} = dGh . W_hh is one 32x256x768 product per workgroup on bf16 MFMAs with
-//     W_hh^T streamed from L2 (384 KB shared by all workgroups) through a register ring.
-//     Bias and W_q gradients are reduced in registers and added once per workgroup.
-// The forward uses the quantized W_hh, the backward the bf16 master copy (straight-through,
-// the usual fp8-training split); weight gradients dW_hh / dW_ih stay split-K GEMMs.
+//     the fused GRU backward writes dGx / dGh (bf16, transposed through LDS) and dGh as an MX-fp8
+//     hi/lo pair (hi = q(x), lo = q(x - hi), each with its own E8M0 scale per 32 gate rows) to LDS,
+//     then dh_{t-1} = dGh . W_hh is one 16x256x768 product per workgroup on the scaled fp8 MFMA, hi
+//     and lo in turn, against W_hh^T resident in VGPRs as MX-fp8 (gru_pack_kernel's whhT8 / whhTs,
+//     32-gate-row blocks per unit).  W_q / b_q gradients are reduced in registers and added once per
+//     workgroup: with atomics onto one row, or each workgroup into its own row of a partials buffer
+//     that gru_qgrad_reduce_kernel sums in order (gq_stride).
+// The forward multiplies with W_hh quantized along K, the backward with W_hh^T quantized along the gate
+// rows (straight-through for the weights); weight gradients dW_hh / dW_ih stay split-K GEMMs on the bf16
+// dGh^T / dGx^T, and gru_grad_fixup_kernel moves the bias gradients out of their ones row / column.
 #include "gru_common.h"
 
 namespace st {

@@ -355,7 +355,8 @@ class RecurrentDQN:
     # ---------------------------------------------------------------- learner
     def update(self, with_act: bool = False, flip: bool = False) -> None:
         """One learner update on B sampled segments: gather -> fused unroll of both nets (MX-fp8) ->
-        TD -> fused BPTT (bf16) -> split-K weight-gradient GEMMs -> Adam -> repack the actor weights.
+        TD -> fused BPTT (16 sequences per workgroup, resident MX-fp8 W_hh^T, dGh as an fp8 hi/lo pair) ->
+        split-K weight-gradient GEMMs -> Adam -> repack the actor weights.
         ``with_act``: the actor launch runs on a side stream right after the gather (see overlap_act).
         ``flip``: re-pack into the other online set without waiting for the actor; the caller then
         switches ``_par`` (the overlapped iteration)."""

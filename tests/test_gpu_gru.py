@@ -56,7 +56,8 @@ def _small(E=64, S=4, eps=0.9, **kw):
     kw.setdefault("ep_len", 5)
     kw.setdefault("batch", 128)
     kw.setdefault("replay_segments", 1024)
-    return RecurrentDQN(_cfg(eps), torch.device("cuda", 0), envs=E, seq=S, burn_in=1, **kw)
+    kw.setdefault("burn_in", 1)
+    return RecurrentDQN(_cfg(eps), torch.device("cuda", 0), envs=E, seq=S, **kw)
 
 
 def test_pack_is_exact_mx_quantization(native_built):
@@ -176,17 +177,34 @@ def _ref_unroll(X, h0, p, D, Wdeq, Wbwd=None):
         z = torch.sigmoid(gx[:, 256:512] + gh[:, 256:512])
         n = torch.tanh(gx[:, 512:] + r * gh[:, 512:])
         h = (1 - z) * n + z * h
-        qs.append(h @ p["w_q"].t() + p["b_q"])
+        # the Q head multiplies bf16-rounded h with bf16-rounded W_q rows (one bf16 MFMA per tile); the
+        # gradients flow straight through both roundings
+        hb = h + (h.detach().to(torch.bfloat16).float() - h.detach())
+        wqb = p["w_q"] + (p["w_q"].detach().to(torch.bfloat16).float() - p["w_q"].detach())
+        qs.append(hb @ wqb.t() + p["b_q"])
         if t < D.shape[0]:
             h = h * (1 - D[t])[:, None]
     return torch.stack(qs)
 
 
-def test_learner_gradients_match_autograd(native_built):
+def _grad_slices(n, t):
+    """A parameter gradient cut the way an error would be confined: the r / z / n gate blocks of the GRU
+    tensors, the action rows of the Q head."""
+    t = t.reshape(768, -1) if n in ("w_ih", "w_hh", "b_ih", "b_hh") else t.reshape(3, -1)
+    k = t.shape[0] // 3
+    return [("rzn"[i] if k > 1 else f"a{i}", t[i * k:(i + 1) * k].reshape(-1)) for i in range(3)]
+
+
+# RecurrentDQN takes batches that are multiples of 128 (its weight-gradient GEMMs' tiles), so the wiring runs at
+# 128: one step without burn-in, a second gather pass (S = 24), the ordered Q-head path at S = 16, burn_in = S - 1.
+# Batches of 32 and 96 reach the kernels directly in tests/test_gpu_gru_learn_kernels.py.
+@pytest.mark.parametrize("batch,seq,burn_in,deterministic", [(128, 4, 1, False), (128, 1, 0, False), (128, 24, 4, False),
+                                                             (128, 16, 4, True), (128, 4, 3, False)])
+def test_learner_gradients_match_autograd(native_built, batch, seq, burn_in, deterministic):
     from sharetrade.ops.gru import unpack_whh, unpack_whhT
     from sharetrade.utils import rng
 
-    d = _small(E=128, S=4, eps=0.5, batch=128)
+    d = _small(E=128, S=seq, eps=0.5, batch=batch, burn_in=burn_in, deterministic=deterministic)
     for _ in range(3):
         d.act()
     P0 = {n: t.detach().clone().cpu() for n, t in d.P.items()}
@@ -231,6 +249,12 @@ def test_learner_gradients_match_autograd(native_built):
         got = d.dP[n].cpu().view(-1)
         rel = float((got - ref).norm() / (ref.norm() + 1e-20))
         assert rel < 5e-2, (n, rel)
+        # the same bound per gate block (r, z, n rows) and per action row: an error confined to one of them
+        # moves the whole tensor's norm by far less
+        for (tag, r_), (_, g_) in zip(_grad_slices(n, ref), _grad_slices(n, got)):
+            rel = float((g_ - r_).norm() / (r_.norm() + 1e-20))
+            print(f"[meas] grad {n}[{tag}] B={batch} S={seq} burn={burn_in}: rel {rel:.4f}")
+            assert rel < 5e-2, (n, tag, rel)
 
 
 def test_graph_iterations_train(native_built):
