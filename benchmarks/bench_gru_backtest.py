@@ -6,7 +6,10 @@
 * ``actor_single`` / ``actor_pair``: the only other way to step a GRU policy, ``RecurrentDQN.act()`` with the
   single-chunk and the two-chunk actor kernel: ``bars / seq`` launches covering the same env-bars (they also
   explore, write replay segments and round-trip ``h`` through HBM every ``seq`` bars);
-* ``rollout_small``: the rollout on the first ``--small-envs`` envs (8,192 = one workgroup per CU).
+* ``rollout_small``: the rollout on the first ``--small-envs`` envs (8,192 = one workgroup per CU);
+* with ``--ledger``: ``rollout_ledger``, the same run through the kernel's ledger instance (``ledger=True``: risk
+  ledger and portfolio curve kept on the chip), and ``trace_then_ledger``, the path it replaces: a ``trace=True``
+  launch followed by ``ledger_from_trace`` on the traced GPU tensors (``trace_only`` is its launch alone).
 
 Every run is warm (one untimed run first) and timed with HIP events around the whole run; reported are the
 median, min and max over ``--repeats`` and ns per env-bar from the median, plus the ratios rollout / actor.
@@ -56,6 +59,9 @@ def main() -> int:
     ap.add_argument("--seq", type=int, default=16, help="bars per actor launch")
     ap.add_argument("--bank-bars", type=int, default=4096, help="bars of the learner's bank")
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--ledger", action="store_true",
+                    help="also time the ledger launch and the trace launch + ledger_from_trace it replaces")
+    ap.add_argument("--no-actors", action="store_true", help="skip the actor runs")
     args = ap.parse_args()
     if args.bars % args.seq:
         ap.error("--bars must be a multiple of --seq")
@@ -65,7 +71,7 @@ def main() -> int:
     build.build_all()
     from sharetrade.config import preset_config
     from sharetrade.ops import gru as G
-    from sharetrade.serve.gru_rollout import GruPolicy
+    from sharetrade.serve.gru_rollout import GruPolicy, ledger_from_trace
     from sharetrade.trainer.recurrent import RecurrentDQN
 
     dev = torch.device("cuda", 0)
@@ -89,11 +95,32 @@ def main() -> int:
     res = pol.backtest(d.close, d.feat, steps=args.bars, ep_len=d.ep_len, cost=d.cost, ret=d.ret)
     out["rollout_summary"] = res.summary()
 
+    if args.ledger:
+        kw = dict(steps=args.bars, ep_len=d.ep_len, cost=d.cost, ret=d.ret)
+
+        def traced(then_ledger):
+            def run():
+                r = pol.backtest(d.close, d.feat, trace=True, **kw)
+                if then_ledger:
+                    ledger_from_trace(r.actions, r.reward, start=0, origin=0, ep_len=d.ep_len)
+            return run
+
+        out["rollout_ledger"] = report(timed(lambda: pol.backtest(d.close, d.feat, ledger=True, **kw), args.repeats),
+                                       env_bars)
+        out["trace_only"] = report(timed(traced(False), args.repeats), env_bars)
+        out["trace_then_ledger"] = report(timed(traced(True), max(1, args.repeats // 2)), env_bars)
+        out["ledger_over_plain"] = round(out["rollout_ledger"]["ms_median"] / out["rollout"]["ms_median"], 4)
+        out["ledger_over_trace_then_ledger"] = round(out["rollout_ledger"]["ms_median"] /
+                                                     out["trace_then_ledger"]["ms_median"], 4)
+        led = pol.backtest(d.close, d.feat, ledger=True, **kw)
+        assert torch.equal(led.ret, res.ret), "the ledger launch's returns differ from the plain launch's"
+        out["ledger_report"] = {k: v for k, v in led.report()["series"].items()}
+
     def act():
         for _ in range(launches):
             d.act()
 
-    for kernel in ("single", "pair"):
+    for kernel in () if args.no_actors else ("single", "pair"):
         d.actor_kernel = kernel
         d.grid = d._auto_grid(dev)
         out[f"actor_{kernel}"] = dict(report(timed(act, args.repeats), env_bars), grid=d.grid)

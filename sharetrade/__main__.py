@@ -166,7 +166,8 @@ def _recurrent_bank(a, cfg: Config, ctx, kw: dict) -> dict:
 def _backtest_gru(a, cfg: Config) -> dict:
     """``backtest`` of a GRU(256) policy on N held-out synthetic minute-bar series (or the bars of ``--bars-file``):
     the greedy policy, always long (Buy on every bar), uniform random and flat, each as mean / std / median of the
-    per-series return."""
+    per-series return.  ``--report`` adds the risk report of each (drawdown, Sharpe, round trips, per-episode and
+    portfolio figures: ``GruBacktestResult.report``), ``--curve-out`` saves the policy's portfolio curve."""
     import os
 
     import numpy as np
@@ -174,7 +175,7 @@ def _backtest_gru(a, cfg: Config) -> dict:
 
     from .data import minute_bars as mb
     from .models import gru_qnet as gq
-    from .serve.gru_rollout import GruPolicy, result_from, simulate_minute_actions
+    from .serve.gru_rollout import GruPolicy, ledger_from_trace, result_from, simulate_minute_actions
     from .trainer.engine import resolve_device
 
     dev = resolve_device(a.device)
@@ -200,19 +201,29 @@ def _backtest_gru(a, cfg: Config) -> dict:
             c, f = mb.generate_numpy(N, T, seed=bars_seed)
             close, feat = torch.from_numpy(c), torch.from_numpy(f).to(torch.bfloat16)
     kw = dict(ep_len=ep_len, cost=float(a.cost))
-    res = pol.backtest(close, feat, trace=bool(a.trace_out), **kw)
+    led = bool(a.report or a.curve_out)   # the risk ledger rides along in the same launch
+    res = pol.backtest(close, feat, trace=bool(a.trace_out), ledger=led, **kw)
     steps = res.steps
-    base = {"uniform_random": pol.backtest(close, feat, greedy=False, epsilon=0.0, **kw).summary()}
+    rnd = pol.backtest(close, feat, greedy=False, epsilon=0.0, ledger=bool(a.report), **kw)
+    base = {"uniform_random": rnd.summary()}
+    reports = {"policy": res.report(), "uniform_random": rnd.report()} if a.report else {}
     for name, act in (("always_long", 0), ("flat", 1)):
-        out = simulate_minute_actions(close, torch.full((N, steps), act, dtype=torch.int8, device=close.device), **kw)
-        base[name] = result_from(out, 0, steps, ep_len, 0, res.backend, False).summary()
+        acts = torch.full((N, steps), act, dtype=torch.int8, device=close.device)
+        out = simulate_minute_actions(close, acts, **kw)
+        bl = ledger_from_trace(acts, out["reward"], start=0, origin=0, ep_len=ep_len) if a.report else None
+        r = result_from(out, 0, steps, ep_len, 0, res.backend, False, bl)
+        base[name] = r.summary()
+        if a.report:
+            reports[name] = r.report()
     if a.trace_out:
         os.makedirs(a.trace_out, exist_ok=True)
         np.save(os.path.join(a.trace_out, "actions.npy"), res.actions.cpu().numpy())
         np.save(os.path.join(a.trace_out, "reward.npy"), res.reward.cpu().numpy())
+    if a.curve_out:
+        np.save(a.curve_out, res.ledger.curve.cpu().numpy())
     return {"policy_kind": "gru", "series": N, "bars": T, "steps": int(steps), "ep_len": ep_len, "cost": float(a.cost),
             "bars_seed": bars_seed, "backend": res.backend, "weights": "checkpoint" if a.ckpt else "init",
-            "policy": res.summary(), **base, **info}
+            "policy": res.summary(), **base, **info, **({"report": reports} if a.report else {})}
 
 
 def main(argv=None) -> int:
@@ -322,6 +333,11 @@ def main(argv=None) -> int:
                            help="GRU policy: seed of the synthetic bars (default: the policy's seed + 1000, held out)")
             p.add_argument("--ep-len", type=int, default=390, help="GRU policy: bars per episode")
             p.add_argument("--cost", type=float, default=0.01, help="GRU policy: cost per position change")
+            p.add_argument("--report", action="store_true",
+                           help="GRU policy: add a `report` block (drawdown, Sharpe, hit rate, per-episode and "
+                                "portfolio figures) for the policy and every baseline")
+            p.add_argument("--curve-out", default=None, metavar="F.npy",
+                           help="GRU policy: write the portfolio curve (per-bar sum of the series' rewards) here")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(level=getattr(logging, cfg.log.loglevel, logging.INFO),

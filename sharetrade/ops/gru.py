@@ -70,6 +70,27 @@ class RolloutArgs(C.Structure):
                 ("key0", C.c_uint32), ("key1", C.c_uint32), ("env_offset", C.c_uint32)]
 
 
+class LedgerOut(C.Structure):
+    """``GruLedgerOut`` of ``csrc/gru_rollout.hip``: what the ledger instance of the rollout writes besides the
+    plain outputs.  ``ep_ret`` / ``ep_trades`` / ``state_out`` / ``stats`` go together, and so do ``part`` /
+    ``curve``; either group may be null, and so may ``state_in`` (a fresh ledger)."""
+    _fields_ = [("ep_ret", C.c_void_p), ("ep_trades", C.c_void_p), ("state_in", C.c_void_p),
+                ("state_out", C.c_void_p), ("stats", C.c_void_p), ("part", C.c_void_p), ("curve", C.c_void_p),
+                ("n_ep", C.c_int), ("part_stride", C.c_int)]
+
+
+class RolloutLedgerArgs(C.Structure):
+    """``GruRolloutLedger``: a ``GruRollout`` followed by the ledger pointers."""
+    _fields_ = [("r", RolloutArgs), ("l", LedgerOut)]
+
+
+# the 32-byte records of the ledger, as columns of int32 [E, 8] tensors (fp32 columns hold the bits)
+LEDGER_STATE_COLS = ("cum", "peak", "trip", "ep", "run", "ep_tr")
+LEDGER_STATE_FLOAT = frozenset({"cum", "peak", "trip", "ep"})
+LEDGER_STATS_COLS = ("max_dd", "sumsq", "win_sum", "loss_sum", "dd_bars", "trips", "wins")
+LEDGER_STATS_FLOAT = frozenset({"max_dd", "sumsq", "win_sum", "loss_sum"})
+
+
 class ServeArgs(C.Structure):
     """``GruServe`` of ``csrc/gru_serve.hip``: B request rows, one bar each, on a table of S session slots."""
     _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
@@ -132,6 +153,7 @@ def lib():
                          ("st_gru_act", [C.POINTER(ActArgs), i, vp]),
                          ("st_gru_act_pair", [C.POINTER(ActArgs), i, vp]),
                          ("st_gru_rollout_launch", [C.POINTER(RolloutArgs), i, vp]),
+                         ("st_gru_rollout_ledger_launch", [C.POINTER(RolloutLedgerArgs), i, vp]),
                          ("st_gru_serve_launch", [C.POINTER(ServeArgs), i, vp]),
                          ("st_gru_gather", [C.POINTER(GatherArgs), vp]),
                          ("st_gru_seq_fwd", [C.POINTER(SeqFwdArgs), vp]),
@@ -149,6 +171,8 @@ def lib():
         L.st_gru_rollout_block.restype = C.c_int
         L.st_gru_serve_lds_bytes.restype = C.c_int
         L.st_gru_seq_bwd_rows.restype = C.c_int
+        L.st_abi_gru_rollout_ledger.argtypes = [C.POINTER(C.c_int), i]
+        L.st_abi_gru_rollout_ledger.restype = C.c_int
         L.st_abi_gru_serve.argtypes = [C.POINTER(C.c_int), i]
         L.st_abi_gru_serve.restype = C.c_int
         L._gru_bound = True

@@ -16,6 +16,13 @@ position goes flat at no cost, the entry price is cleared and ``h`` restarts fro
 
 A run can be cut into pieces: pass a piece's final ``h`` / ``position`` / ``entry`` and the next ``start``
 with the same ``origin``; the pieces reproduce the whole bit for bit.
+
+``ledger=True`` also keeps the risk ledger on the chip (the ledger instance of the kernel): per series the
+running equity curve's peak, deepest and longest drawdown and sum of squared rewards, every episode's return and
+trades, the round trips and their wins, and the portfolio's per-bar sum of rewards (:class:`GruLedger`).
+:func:`ledger_from_trace` is the same arithmetic in PyTorch float32 on a trace: the ``torch`` backend's ledger,
+the kernel's oracle (bit for bit) and the ledger of the baselines.  ``GruBacktestResult.report()`` turns a ledger
+into drawdown, Sharpe, hit rate, per-episode and portfolio figures.
 """
 from __future__ import annotations
 
@@ -23,7 +30,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, Iterable, Optional, Union
+from typing import Dict, Iterable, List, Optional, Union
 
 import numpy as np
 import torch
@@ -254,6 +261,180 @@ def reference_gru_rollout(params: Dict[str, torch.Tensor], close: torch.Tensor, 
             "h": h.float(), "actions": actions, "q": qs, "reward": reward}
 
 
+CHUNK = G.RN   # envs whose rewards one workgroup sums per bar (the kernel's 32-env chunk)
+
+
+def episode_columns(start: int, steps: int, origin: int, ep_len: int):
+    """(es0, n_ep, full): the start of the episode that holds bar ``start``, the episode columns bars
+    ``start .. start + steps - 1`` touch, and per column whether all ``ep_len`` of its bars lie in the run."""
+    es0 = origin + (start - origin) // ep_len * ep_len
+    n_ep = (start + steps - 1 - es0) // ep_len + 1
+    full = [es0 + k * ep_len >= start and es0 + (k + 1) * ep_len <= start + steps for k in range(n_ep)]
+    return es0, n_ep, full
+
+
+@dataclass
+class GruLedger:
+    """The risk ledger of one run (piece): what ``csrc/gru_rollout.hip``'s ledger instance keeps per series.
+
+    ``state`` continues a cut run (``ledger_state=`` of the next piece); the other per-series fields are of this
+    piece alone, with drawdowns measured on the curve carried in through ``state``."""
+
+    ep_ret: torch.Tensor      # [E, n_ep] fp32 return of every episode column
+    ep_trades: torch.Tensor   # [E, n_ep] int32 position changes of every episode column
+    max_dd: torch.Tensor      # [E] fp32 deepest peak - cum (the peak starts at 0)
+    dd_bars: torch.Tensor     # [E] int32 longest stretch of bars with cum < peak
+    sumsq: torch.Tensor       # [E] fp32 sum of squared rewards
+    trips: torch.Tensor       # [E] int32 closed round trips (a long forced flat at an episode end closes)
+    wins: torch.Tensor        # [E] int32 closed trips with a positive sum of rewards
+    win_sum: torch.Tensor     # [E] fp32 sum of the winning trips
+    loss_sum: torch.Tensor    # [E] fp32 sum of the other trips (<= 0)
+    state: torch.Tensor       # [E, 8] int32 records {cum, peak, trip, ep (fp32 bits), run, ep_tr, 0, 0}
+    full: List[bool]          # per column: a whole episode (the first and last may be partial)
+    curve: Optional[torch.Tensor] = None   # [steps] fp32 sum over the series of the bar's rewards
+
+    def state_field(self, name: str) -> torch.Tensor:
+        """Column ``name`` of ``state`` (``cum``, ``peak``, ``trip``, ``ep`` as fp32; ``run``, ``ep_tr`` int32)."""
+        col = self.state[:, G.LEDGER_STATE_COLS.index(name)]
+        return col.view(torch.float32) if name in G.LEDGER_STATE_FLOAT else col
+
+
+def _ledger_of_records(ep_ret, ep_trades, stats, state, full, curve) -> GruLedger:
+    f = {n: (stats[:, i].view(torch.float32) if n in G.LEDGER_STATS_FLOAT else stats[:, i])
+         for i, n in enumerate(G.LEDGER_STATS_COLS)}
+    return GruLedger(ep_ret=ep_ret, ep_trades=ep_trades, state=state, full=full, curve=curve, **f)
+
+
+def chunk_sums(reward: torch.Tensor) -> torch.Tensor:
+    """[chunks, steps]: per bar the sum of every 32-series chunk's rewards by the kernel's butterfly (lanes 16,
+    8, 4, 2, 1 apart), rows past E contributing 0."""
+    E, steps = reward.shape
+    nch = -(-E // CHUNK)
+    v = torch.zeros(nch * CHUNK, steps, dtype=torch.float32, device=reward.device)
+    v[:E] = reward
+    v = v.view(nch, CHUNK, steps)
+    for w in (16, 8, 4, 2, 1):
+        v = v[:, :w] + v[:, w:2 * w]
+    return v[:, 0]
+
+
+def curve_from_chunks(part: torch.Tensor) -> torch.Tensor:
+    """[steps]: the chunks' partial sums added in ascending order from 0 (``gru_curve_reduce_kernel``)."""
+    curve = torch.zeros(part.shape[1], dtype=torch.float32, device=part.device)
+    for c in range(part.shape[0]):
+        curve = curve + part[c]
+    return curve
+
+
+def ledger_from_trace(actions: torch.Tensor, reward: torch.Tensor, *, position: Optional[torch.Tensor] = None,
+                      start: int, origin: int, ep_len: int, ledger_state: Optional[torch.Tensor] = None,
+                      curve: bool = True) -> GruLedger:
+    """The ledger of a traced run: ``actions`` [E, steps] (0 Buy, 1 Sell, 2 Hold) and ``reward`` [E, steps] of
+    bars ``start .. start + steps - 1``, ``position`` [E] the position before bar ``start`` (None: flat).
+
+    Float32 in the kernel's order, operation by operation (every product is rounded before it is added), so a
+    ledger launch equals this on its own trace bit for bit.  After bar t gives ``reward``, ``trade`` and
+    ``position'``:
+
+    * curve: ``cum += reward``; ``peak = cum if cum > peak``; ``max_dd`` the largest ``peak - cum``; ``run`` counts
+      the bars since ``cum < peak`` began and ``dd_bars`` is its maximum; ``sumsq += reward * reward``;
+    * episodes: ``ep += reward``, ``ep_tr += trade``, stored in column k on an episode's last bar and on the run's
+      last bar; an episode's last bar then clears both and moves to column k + 1;
+    * round trips: a bar that opens a long starts ``trip = reward``; any other bar that began long adds its
+      reward (a Sell's cost included); a Sell from long, or an episode end with a long held (flat at no cost),
+      closes the trip: ``trips``, ``wins`` if ``trip > 0``, ``win_sum`` / ``loss_sum``, ``trip = 0``.
+
+    ``ledger_state`` [E, 8] int32 (``GruLedger.state`` of the piece before) continues a cut run exactly."""
+    R = reward.float()
+    E, steps = (int(v) for v in R.shape)
+    dev = R.device
+    A = actions.to(dev)
+    start, origin, ep_len = int(start), int(origin), int(ep_len)
+    es0, n_ep, full = episode_columns(start, steps, origin, ep_len)
+    i32, f32 = torch.int32, torch.float32
+    if ledger_state is None:
+        st = torch.zeros(E, 8, dtype=i32, device=dev)
+    else:
+        st = ledger_state.to(dev, i32).contiguous().clone()
+        if tuple(st.shape) != (E, 8):
+            raise ValueError(f"ledger_state must be [E, 8] = {(E, 8)}, got {tuple(st.shape)}")
+    fl = st[:, :4].contiguous().view(f32)
+    cum, peak, trip, ep = (fl[:, j].clone() for j in range(4))
+    run, ep_tr = st[:, 4].clone(), st[:, 5].clone()
+    pz = torch.zeros(E, dtype=i32, device=dev) if position is None else position.to(dev, i32).clone()
+    zf, zi, one = torch.zeros(E, dtype=f32, device=dev), torch.zeros(E, dtype=i32, device=dev), \
+        torch.ones(E, dtype=i32, device=dev)
+    mdd, ssq, wsum, lsum = zf.clone(), zf.clone(), zf.clone(), zf.clone()
+    ddb, trips, wins = zi.clone(), zi.clone(), zi.clone()
+    ep_ret = torch.zeros(E, n_ep, dtype=f32, device=dev)
+    ep_trades = torch.zeros(E, n_ep, dtype=i32, device=dev)
+    es, k = es0, 0
+    for i in range(steps):
+        t = start + i
+        done = (t + 1 - es) >= ep_len
+        a, rw = A[:, i], R[:, i]
+        np_ = torch.where(a == 0, one, torch.where(a == 1, zi, pz))
+        trade = np_ != pz
+        # running curve
+        cum = cum + rw
+        peak = torch.where(cum > peak, cum, peak)
+        dd = peak - cum
+        mdd = torch.where(dd > mdd, dd, mdd)
+        run = torch.where(cum < peak, run + 1, zi)
+        ddb = torch.maximum(ddb, run)
+        ssq = ssq + rw * rw
+        # episode ledger
+        ep = ep + rw
+        ep_tr = ep_tr + trade.to(i32)
+        if done or i == steps - 1:
+            ep_ret[:, k] = ep
+            ep_trades[:, k] = ep_tr
+        if done:
+            ep, ep_tr = zf.clone(), zi.clone()
+        # round trips
+        opens = trade & (np_ == 1)
+        trip = torch.where(opens, rw, torch.where(pz != 0, trip + rw, trip))
+        closes = trade & (np_ == 0)
+        if done:
+            closes = closes | (np_ == 1)
+        won = trip > 0
+        trips = trips + closes.to(i32)
+        wins = wins + (closes & won).to(i32)
+        wsum = torch.where(closes & won, wsum + trip, wsum)
+        lsum = torch.where(closes & ~won, lsum + trip, lsum)
+        trip = torch.where(closes, zf, trip)
+        pz = zi.clone() if done else np_
+        if done:
+            es, k = t + 1, k + 1
+    state = torch.zeros(E, 8, dtype=i32, device=dev)
+    state[:, :4] = torch.stack([cum, peak, trip, ep], dim=1).view(i32)
+    state[:, 4], state[:, 5] = run, ep_tr
+    return GruLedger(ep_ret=ep_ret, ep_trades=ep_trades, max_dd=mdd, dd_bars=ddb, sumsq=ssq, trips=trips, wins=wins,
+                     win_sum=wsum, loss_sum=lsum, state=state, full=full,
+                     curve=curve_from_chunks(chunk_sums(R)) if curve else None)
+
+
+def _div(a: float, b: float) -> Optional[float]:
+    return None if b == 0 else a / b
+
+
+def _sharpe(total: float, sumsq: float, n: int, bars_per_year: float) -> Optional[float]:
+    """Annualised per-bar Sharpe ratio from the sum and the sum of squares of n per-bar returns."""
+    m = total / n
+    var = sumsq / n - m * m
+    return None if var <= 0.0 else m / math.sqrt(var) * math.sqrt(bars_per_year)
+
+
+def _moments(x: torch.Tensor) -> Dict[str, Optional[float]]:
+    """mean / population std / worst / share positive of a float64 sample (None when it is empty)."""
+    n = int(x.numel())
+    if n == 0:
+        return {"n": 0, "mean": None, "std": None, "worst": None, "positive": None}
+    m = float(x.sum()) / n
+    return {"n": n, "mean": m, "std": math.sqrt(max(0.0, float((x * x).sum()) / n - m * m)),
+            "worst": float(x.min()), "positive": float((x > 0).sum()) / n}
+
+
 @dataclass
 class GruBacktestResult:
     """What a GRU policy did over ``steps`` bars from bar ``start`` of every series: per-env tensors and, when
@@ -273,6 +454,7 @@ class GruBacktestResult:
     actions: Optional[torch.Tensor] = None   # [E, steps] int8
     q: Optional[torch.Tensor] = None         # [E, steps, 3] fp32
     reward: Optional[torch.Tensor] = None    # [E, steps] fp32
+    ledger: Optional[GruLedger] = None       # the risk ledger (``ledger=True``)
 
     def summary(self) -> Dict[str, float]:
         """Mean / population std / median of the per-env return (the median is an element of the sample),
@@ -285,14 +467,63 @@ class GruBacktestResult:
                 "median": float(r.median()), "per_episode": m * self.ep_len / self.steps, "steps": int(self.steps),
                 "trades": int(self.trades.sum()), "long_frac": float(self.long.sum()) / (n * self.steps)}
 
+    def report(self, bars_per_year: Optional[float] = None) -> Dict[str, object]:
+        """The risk report of a run made with ``ledger=True``, computed in float64 on the host; a ratio with a
+        zero denominator is None.  ``bars_per_year`` (default ``252 * ep_len``) annualises the Sharpe ratios.
 
-def result_from(out: Dict[str, torch.Tensor], start, steps, ep_len, origin, backend, trace) -> GruBacktestResult:
+        * ``series``: mean / median return, mean / worst ``max_dd``, the longest drawdown in bars, mean / median
+          of the per-series Sharpe ratio (from the piece's return, ``cum`` of a fresh ledger, and ``sumsq``;
+          series with zero variance left out), and over all series' round trips the hit rate ``wins / trips``,
+          the profit factor ``win_sum / |loss_sum|`` and the mean trip;
+        * ``episodes``: mean / std / worst / share positive of the (series, full episode) returns;
+        * ``portfolio`` (None without a curve): the equal-weight book ``curve / E``: total, max drawdown (peak
+          from 0), Sharpe, and the return of every episode column with ``full`` telling the whole ones."""
+        L = self.ledger
+        if L is None:
+            raise ValueError("report() needs a backtest made with ledger=True")
+        bpy = float(252 * self.ep_len if bars_per_year is None else bars_per_year)
+        n, steps = int(self.ret.numel()), int(self.steps)
+        r = self.ret.double().cpu()
+        mdd = L.max_dd.double().cpu()
+        ssq = L.sumsq.double().cpu()
+        sh = [v for v in (_sharpe(float(a), float(b), steps, bpy) for a, b in zip(r.tolist(), ssq.tolist()))
+              if v is not None]
+        trips, wins = int(L.trips.sum()), int(L.wins.sum())
+        wsum, lsum = float(L.win_sum.double().sum()), float(L.loss_sum.double().sum())
+        series = {"n": n, "ret_mean": float(r.sum()) / n, "ret_median": float(r.median()),
+                  "max_dd_mean": float(mdd.sum()) / n, "max_dd_worst": float(mdd.max()),
+                  "dd_bars_longest": int(L.dd_bars.max()),
+                  "sharpe_mean": _div(sum(sh), len(sh)), "sharpe_median": float(np.median(sh)) if sh else None,
+                  "trips": trips, "hit_rate": _div(wins, trips), "profit_factor": _div(wsum, abs(lsum)),
+                  "trip_mean": _div(wsum + lsum, trips)}
+        full = [k for k, f in enumerate(L.full) if f]
+        episodes = _moments(L.ep_ret.double().cpu()[:, full].flatten())
+        portfolio = None
+        if L.curve is not None:
+            c = L.curve.double().cpu() / n
+            eq = torch.cumsum(c, 0)
+            peak = torch.cummax(torch.clamp(eq, min=0.0), 0).values
+            es0 = episode_columns(self.start, steps, self.origin, self.ep_len)[0]
+            cols = []
+            for k in range(len(L.full)):
+                lo = max(es0 + k * self.ep_len, self.start) - self.start
+                hi = min(es0 + (k + 1) * self.ep_len, self.start + steps) - self.start
+                cols.append(float(c[lo:hi].sum()))
+            portfolio = {"total": float(c.sum()), "max_dd": float((peak - eq).max()),
+                         "sharpe": _sharpe(float(c.sum()), float((c * c).sum()), steps, bpy),
+                         "episodes": cols, "full": list(L.full)}
+        return {"bars_per_year": bpy, "series": series, "episodes": episodes, "portfolio": portfolio}
+
+
+def result_from(out: Dict[str, torch.Tensor], start, steps, ep_len, origin, backend, trace,
+                ledger: Optional[GruLedger] = None) -> GruBacktestResult:
     """The fields of :func:`reference_gru_rollout` / :func:`simulate_minute_actions` as a result object."""
     return GruBacktestResult(ret=out["ret"], trades=out["trades"], long=out["long"], position=out["position"],
                              entry=out["entry"], h=out.get("h"), start=int(start), steps=int(steps),
                              ep_len=int(ep_len), origin=int(origin), backend=backend,
                              actions=out["actions"] if trace else None,
-                             q=out["q"] if trace else None, reward=out["reward"] if trace else None)
+                             q=out["q"] if trace else None, reward=out["reward"] if trace else None,
+                             ledger=ledger)
 
 
 def _run_dir(path: str) -> str:
@@ -415,14 +646,20 @@ class GruPolicy:
                  epsilon: Optional[float] = None, h0: Optional[torch.Tensor] = None,
                  position: Optional[torch.Tensor] = None, entry: Optional[torch.Tensor] = None, trace: bool = False,
                  env_offset: int = 0, backend: str = "auto", grid: int = 0,
-                 ret: Optional[torch.Tensor] = None) -> GruBacktestResult:
+                 ret: Optional[torch.Tensor] = None, ledger: bool = False,
+                 ledger_state: Optional[torch.Tensor] = None) -> GruBacktestResult:
         """Run the policy over bars ``start .. start + steps - 1`` (default: to the last bar with a next
         close) of ``close`` [E, T] fp32 and ``feat`` [E, T, 8] bf16, episodes of ``ep_len`` bars counted from
         ``origin`` (default ``start``).  ``greedy`` (default) takes the first maximum of Q; else the epsilon
         rule with ``epsilon`` (default the policy's own; 0 = uniform random).  ``h0`` [E, 256] fp32,
         ``position`` [E] int32 and ``entry`` [E] fp32 continue an earlier piece.  ``backend``: ``hip`` (one
         launch on the current stream), ``torch`` (:func:`reference_gru_rollout`) or ``auto``.  ``ret`` [E, T]
-        fp32: ``minute_bars.bar_returns(close)`` when the caller already holds it (else computed here)."""
+        fp32: ``minute_bars.bar_returns(close)`` when the caller already holds it (else computed here).
+        ``ledger``: also keep the risk ledger (``result.ledger``, a :class:`GruLedger`; the kernel's ledger
+        instance, nothing more is written per bar than one partial sum per 32 series); ``ledger_state`` [E, 8]
+        int32 is ``ledger.state`` of the piece before."""
+        if ledger_state is not None and not ledger:
+            raise ValueError("ledger_state continues a ledger: pass ledger=True")
         if backend not in ("auto", "hip", "torch"):
             raise ValueError(f"backend must be auto/hip/torch, got {backend!r}")
         if backend == "auto":
@@ -437,12 +674,14 @@ class GruPolicy:
                                         steps=steps, ep_len=ep_len, cost=cost, origin=origin, epsilon=eps,
                                         seed=self.seed, h0=h0, position=position, entry=entry, env_offset=env_offset,
                                         ret=ret)
-            return result_from(out, start, steps, ep_len, origin, "torch", trace)
+            led = ledger_from_trace(out["actions"], out["reward"], position=position, start=start, origin=origin,
+                                    ep_len=ep_len, ledger_state=ledger_state) if ledger else None
+            return result_from(out, start, steps, ep_len, origin, "torch", trace, led)
         return self._backtest_hip(close, feat, start, steps, ep_len, cost, origin, eps, h0, position, entry, trace,
-                                  env_offset, grid, ret)
+                                  env_offset, grid, ret, ledger, ledger_state)
 
     def _backtest_hip(self, close, feat, start, steps, ep_len, cost, origin, eps, h0, position, entry, trace,
-                      env_offset, grid, ret) -> GruBacktestResult:
+                      env_offset, grid, ret, ledger=False, ledger_state=None) -> GruBacktestResult:
         from ..ops import native
 
         if self.packed is None:
@@ -454,7 +693,8 @@ class GruPolicy:
         if feat.dtype != torch.bfloat16 or feat.device != dev or not feat.is_contiguous():
             raise ValueError("feat must be a contiguous bf16 [E, T, 8] tensor on the policy's device")
         for name, t, dt, shp in (("h0", h0, torch.float32, (E, G.HID)), ("position", position, torch.int32, (E,)),
-                                 ("entry", entry, torch.float32, (E,)), ("ret", ret, torch.float32, (E, T))):
+                                 ("entry", entry, torch.float32, (E,)), ("ret", ret, torch.float32, (E, T)),
+                                 ("ledger_state", ledger_state, torch.int32, (E, 8))):
             if t is not None and (t.dtype != dt or tuple(t.shape) != shp or t.device != dev or not t.is_contiguous()):
                 raise ValueError(f"{name} must be a contiguous {dt} device tensor of shape {shp}")
         with torch.cuda.device(dev):
@@ -468,7 +708,8 @@ class GruPolicy:
                 out["actions"] = torch.empty(E, steps, dtype=torch.int8, device=dev)
                 out["q"] = torch.empty(E, steps, 3, device=dev)
                 out["reward"] = torch.empty(E, steps, device=dev)
-            a = G.RolloutArgs()
+            args = G.RolloutLedgerArgs() if ledger else G.RolloutArgs()
+            a = args.r if ledger else args
             for n, t in self.packed.items():
                 setattr(a, n, t.data_ptr())
             a.feat, a.close, a.ret = feat.data_ptr(), close.data_ptr(), ret.data_ptr()
@@ -483,9 +724,25 @@ class GruPolicy:
             a.env_offset = int(env_offset) & 0xFFFFFFFF
             if grid <= 0:
                 grid = self._auto_grid(E)
-            native.check(G.lib().st_gru_rollout_launch(C.byref(a), int(grid), native.stream_handle()),
-                         "st_gru_rollout_launch")
-        return result_from(out, start, steps, ep_len, origin, "hip", trace)
+            led = None
+            if ledger:
+                _, n_ep, full = episode_columns(start, steps, origin, int(ep_len))
+                i32 = torch.int32
+                stride = -(-steps // CHUNK) * CHUNK
+                ep_ret, ep_trades = torch.empty(E, n_ep, device=dev), torch.empty(E, n_ep, dtype=i32, device=dev)
+                state, stats = torch.empty(E, 8, dtype=i32, device=dev), torch.empty(E, 8, dtype=i32, device=dev)
+                part, curve = torch.empty(-(-E // G.RN), stride, device=dev), torch.empty(steps, device=dev)
+                l = args.l
+                l.ep_ret, l.ep_trades, l.state_in = ep_ret.data_ptr(), ep_trades.data_ptr(), native.ptr(ledger_state)
+                l.state_out, l.stats, l.part, l.curve = (t.data_ptr() for t in (state, stats, part, curve))
+                l.n_ep, l.part_stride = n_ep, stride
+                native.check(G.lib().st_gru_rollout_ledger_launch(C.byref(args), int(grid), native.stream_handle()),
+                             "st_gru_rollout_ledger_launch")
+                led = _ledger_of_records(ep_ret, ep_trades, stats, state, full, curve)
+            else:
+                native.check(G.lib().st_gru_rollout_launch(C.byref(a), int(grid), native.stream_handle()),
+                             "st_gru_rollout_launch")
+        return result_from(out, start, steps, ep_len, origin, "hip", trace, led)
 
     def _auto_grid(self, E: int) -> int:
         """Workgroups: one per 32-env chunk up to one per CU, then the fewest that finish the chunks in the same

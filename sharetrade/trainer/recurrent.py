@@ -575,7 +575,8 @@ class RecurrentDQN:
         """The current online (or target) net, frozen and greedy, over whole episodes of bars it was not trained
         on: by default ``envs`` series of ``bars`` (default 4 episodes + 1) bars from the generator's seed
         ``seed + 1000``.  One launch of ``csrc/gru_rollout.hip``; reads the parameters and touches none of the
-        learner's state (envs, replay, recurrent state, counters).  ``kw`` goes to ``GruPolicy.backtest``."""
+        learner's state (envs, replay, recurrent state, counters).  ``kw`` goes to ``GruPolicy.backtest``
+        (``ledger=True`` / ``ledger_state=`` for the risk ledger, ``trace=True``, ``start`` / ``steps`` ...)."""
         from ..serve.gru_rollout import GruPolicy
 
         pol = GruPolicy.from_learner(self, net=net)
