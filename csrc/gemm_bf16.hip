@@ -52,6 +52,7 @@ struct GemmArgs {
   // (plain stores, no atomics; the optimizer sums the M / WM rows)
   float* colpart;
   int ldcp;
+  int ncp;               // rows colpart holds (checked: M / WM of the launch's tile, WM = BM / NWM)
   // EPI_BF16 (2-stage gemm_body tiles) only, optional: the next layer's output head folded into this epilogue --
   // per row m and head row a < nq, the fp32 sum over each wave's WN columns of the stored (bf16) value times
   // qw[a][n]: qpart[(part * M + m) * 4 + a], part = n / WN (N / WN parts, plain stores; the consumer sums the
@@ -856,13 +857,14 @@ static hipError_t launch_gemm_w4(const GemmArgs& p, hipStream_t s) {
 //       6 = 256x256 (4 waves of 128x128, one block per CU; no transposed output)
 // shape / stride / epilogue checks of one product for a BM x BN tile (the kernel assumes whole tiles)
 static bool gemm_args_ok(const st::GemmArgs* p, int epi, int bm, int bn, bool has_t) {
+  const int wm = bm / ((bm >= 256 && bn < 256) ? 4 : 2);   // GemmGeo::WM = BM / NWM: rows per colpart partial
   if (!has_t && p->outT) return false;
   if (p->M % bm || p->N % bn || p->K % st::GBK || p->M <= 0 || p->N <= 0 || p->K <= 0) return false;
   if (p->lda % 8 || p->ldb % 8 || (epi != st::EPI_F32 && p->ldo % 8)) return false;
   if (p->outT && (p->ldoT % 8 || epi == st::EPI_F32)) return false;
   if (epi == st::EPI_RELU_GRAD && (!p->auxT || p->ldaux % 4)) return false;
   if (p->splitk > 1 && (epi != st::EPI_F32 || (p->K / st::GBK) % p->splitk)) return false;
-  if (p->colpart && (epi != st::EPI_RELU_GRAD || p->ldcp < p->N)) return false;
+  if (p->colpart && (epi != st::EPI_RELU_GRAD || p->ldcp < p->N || p->ncp != p->M / wm)) return false;
   if (p->qpart && (epi != st::EPI_BF16 || !p->qw || p->nq < 1 || p->nq > 4 || p->ldqw < p->N || p->splitk > 1 ||
                    p->nqp != p->N / (bn / 2)))   // (every gemm_body tile has 2 wave columns: WN = BN / 2)
     return false;

@@ -68,4 +68,15 @@ def test_epilogue_side_outputs_are_validated_before_launch():
     g = gm.make_args(A, B, out16, gm.EPI_BF16, qhead=(qw, qp))
     assert (g.nq, g.nqp, g.ldqw) == (3, 4, 256) and g.qpart == qp.data_ptr() and g.qw == qw.data_ptr()
     plain = gm.make_args(A, B, out16, gm.EPI_BF16)
-    assert not plain.qpart and not plain.colpart and plain.nqp == 0
+    assert not plain.qpart and not plain.colpart and plain.nqp == 0 and plain.ncp == 0
+    # colpart's row count travels to the launcher, which refuses any but M / WM of its tile (as nqp for qpart)
+    for rows in (2, 4, 8):
+        cp = _t(rows, 264, dtype=torch.float32)[:, :256]
+        g = gm.make_args(A, B, out16, gm.EPI_RELU_GRAD, auxT=_t(256, 256), colpart=cp)
+        assert (g.ncp, g.ldcp) == (rows, 264) and g.colpart == cp.data_ptr()
+
+
+def test_colpart_field_sits_in_the_struct_padding():
+    """ncp follows ldcp in what was padding before the qw pointer: no later field moved."""
+    assert gm.GemmArgs.ncp.offset == gm.GemmArgs.ldcp.offset + 4
+    assert gm.GemmArgs.qw.offset == gm.GemmArgs.ldcp.offset + 8 and gm.GemmArgs.qw.offset % 8 == 0
