@@ -24,7 +24,7 @@
 // The bar itself (weight prologue: gru_weights.h; net on one 16-env tile: gru_net_tile.h; Q row: gru_common.h) is
 // defined once for both actors here, the backtest (gru_rollout.hip) and the server (gru_serve.hip); the trading
 // rule is minute_rule.h's, and the actors' env step (act_step) is one function for both.
-// Learner: csrc/gru_learn.hip.
+// Learner: csrc/gru_learn.hip; its forward includes the same prologue and tile.
 #include "gru_common.h"
 #include "minute_rule.h"
 
@@ -175,12 +175,7 @@ __global__ void __launch_bounds__(256) gru_pack_kernel(GruPack p) {
 }
 
 // ---------------------------------------------------------------- actor
-struct GruAct {
-  const i8v* whh8;
-  const int* whhs;
-  const s8v* wih;
-  const float* bias4;
-  const float* wq;
+struct GruAct : GruNetW {      // the packed weights first (gru_common.h)
   const bf16_t* feat;          // [E][T][RMF]
   const float* close;          // [E][T]
   const float* ret;            // [E][T]: (close[t+1] / close[t] - 1) * 100 (last bar 0)
@@ -210,6 +205,7 @@ struct GruAct {
   unsigned* done_ctr;          // optional (pair actor): workgroups finished; the last one advances rctrl /
                                // ctrl itself and re-zeroes it (else a separate advance launch follows)
 };
+ST_FOLLOWS_NETW(GruAct, feat)
 
 struct ActLds {
   static constexpr int WX = 0;                                   // RW*6*64 s8v

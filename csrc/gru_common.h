@@ -1,7 +1,8 @@
 // Shared pieces of the GRU(256) recurrent Q-net kernels (BASELINE config 5):
-// the MX-fp8 helpers of the actors (gru.hip) and the fused learner (gru_learn.hip), and, with gru_weights.h and
-// gru_net_tile.h, the one definition of the policy's bar that the actors, the backtest (gru_rollout.hip) and the
-// server (gru_serve.hip) all run.
+// the MX-fp8 helpers of the actors (gru.hip) and the fused learner (gru_learn.hip), the packed weights of one net
+// as every launch struct carries them (GruNetW), and, with gru_weights.h and gru_net_tile.h, the one definition of
+// the policy's bar that the actors, the backtest (gru_rollout.hip), the server (gru_serve.hip) and the learner's
+// forward (gru_seq_fwd_kernel, gru_learn.hip) all run.
 #pragma once
 #include "common.h"
 
@@ -20,6 +21,27 @@ constexpr int RT = RW * 64;
 constexpr int XS = RF + 8;         // sX row stride (bf16) = 80 B: conflict-free ds_read_b128
 constexpr int HS = RH + 16;        // sH8 row stride (bytes) = 272 B
 constexpr int SCS = 9;             // scale row stride (ints)
+
+// The packed weights of one net (gru_pack_kernel's layout, GruPack of gru.hip).  The launch structs of the actors,
+// the backtest and the server derive from it, so p.whh8 .. p.wq read the same in every kernel and in
+// gru_weights.h; the learner's forward holds two, online and target.
+struct GruNetW {
+  const i8v* whh8;
+  const int* whhs;
+  const s8v* wih;
+  const float* bias4;
+  const float* wq;
+};
+inline bool net_ok(const GruNetW& w) {   // host: a launcher refuses a net with a null pointer
+  return w.whh8 != nullptr && w.whhs != nullptr && w.wih != nullptr && w.bias4 != nullptr && w.wq != nullptr;
+}
+// The host mirrors (sharetrade/ops/gru.py) lay a derived launch struct out as the weights, then its own members:
+// member M, the first of T's own, must sit at sizeof(GruNetW).  (offsetof into a derived struct is conditionally
+// supported; clang computes it and warns.)
+#define ST_FOLLOWS_NETW(T, M)                                                                        \
+  _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winvalid-offsetof\"")        \
+  static_assert(__builtin_offsetof(T, M) == sizeof(GruNetW), #T "::" #M " must follow the weights"); \
+  _Pragma("clang diagnostic pop")
 
 // ---------------------------------------------------------------- MX-fp8 helpers
 ST_DEV f4v mx_mfma(const i8v& a, const i8v& b, f4v c, int sa, int sb) {
@@ -97,7 +119,9 @@ ST_DEV void quant_h(const float (&hr)[2][2][4], unsigned char* sH8, int* sSc, in
 // ---------------------------------------------------------------- one bar of the GRU(256) policy
 // The per-bar arithmetic of the actors (gru.hip), the backtest (gru_rollout.hip) and the server (gru_serve.hip):
 // one definition, so the four kernels cannot drift apart.  A workgroup is 8 waves on a 32-env chunk; wave w owns
-// hidden units 32w .. 32w+31 of all three gates.  The callers keep their LDS layouts.
+// hidden units 32w .. 32w+31 of all three gates.  The callers keep their LDS layouts.  The learner's forward
+// (gru_seq_fwd_kernel, gru_learn.hip) includes the two statement headers as well, with a chunk of 32 sequences; it
+// keeps a written-out copy of gru_q_row's sum (why: see there).
 
 // Two pieces are statements that each kernel includes in place, not functions (why: see the files): the weight
 // prologue, gru_weights.h, which declares Wh, Ws4, myWx and WqA, and the net on ONE 16-env tile n of the chunk --

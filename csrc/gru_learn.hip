@@ -98,14 +98,6 @@ __global__ void __launch_bounds__(256) gru_gather_kernel(GruGather g) {
 }
 
 // ---------------------------------------------------------------- fused forward
-struct GruNetW {
-  const i8v* whh8;
-  const int* whhs;
-  const s8v* wih;
-  const float* bias4;
-  const float* wq;
-};
-
 struct GruSeqFwd {
   GruNetW on, tg;       // online / target packed weights (gru_pack_kernel layout)
   const bf16_t* X;      // [(S+1)B][RFL]
@@ -147,14 +139,21 @@ ST_DEV void unpack8_bf(uint4 u, float (&v)[8]) {
   v[6] = __uint_as_float(u.w << 16); v[7] = __uint_as_float(u.w & 0xFFFF0000u);
 }
 
-__global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd p) {
+// The bar is the actors': the weight prologue (gru_weights.h) and the net on a 16-sequence tile (gru_net_tile.h) are
+// the source the actors, the backtest and the server run, so the TD targets are evaluated with the function the
+// actor acts with.  The learner's own: x prefetch, the done mask, the h^T staging, the saves, and its copy of the
+// Q-row sum (see there).
+static_assert(LB == RN, "gru_net_tile.h indexes the Q partials with the actors' chunk of RN rows");
+
+__global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd args) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const s8v* sWx = reinterpret_cast<const s8v*>(lds + FwdLds::WX);
   bf16_t* sX = reinterpret_cast<bf16_t*>(lds + FwdLds::X);
   unsigned char* sH8 = lds + FwdLds::H8;
   int* sSc = reinterpret_cast<int*>(lds + FwdLds::SC);
   float* sB = reinterpret_cast<float*>(lds + FwdLds::B);
   float* sWq = reinterpret_cast<float*>(lds + FwdLds::WQ);
-  float* sQp = reinterpret_cast<float*>(lds + FwdLds::QP);
+  float* sQp2 = reinterpret_cast<float*>(lds + FwdLds::QP);   // [2]: a step's partials are read after its barrier
   bf16_t* sHT = reinterpret_cast<bf16_t*>(lds + FwdLds::HT);
   const int tid = threadIdx.x, lane = tid & 63, l16 = lane & 15, g4 = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -171,42 +170,14 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd p) {
   auto flush_h = [&](const bf16_t* st, int blk) {
     for (int c = tid; c < RH * (LB / 8); c += RT) {
       const int u = c / (LB / 8), j = c % (LB / 8);
-      *reinterpret_cast<uint4*>(p.HT + (size_t)u * p.ldht + (size_t)blk * p.B + blockIdx.x * LB + 8 * j) =
+      *reinterpret_cast<uint4*>(args.HT + (size_t)u * args.ldht + (size_t)blk * args.B + blockIdx.x * LB + 8 * j) =
           *reinterpret_cast<const uint4*>(st + u * LB + 8 * j);
     }
   };
-  const i8v* whh8 = online ? p.on.whh8 : p.tg.whh8;
-  const int* whhs = online ? p.on.whhs : p.tg.whhs;
-  const s8v* wih = online ? p.on.wih : p.tg.wih;
-  const float* bias4 = online ? p.on.bias4 : p.tg.bias4;
-  const float* wq = online ? p.on.wq : p.tg.wq;
-  float* Qout = online ? p.Q : p.Qt;
-  const int B = p.B, S = p.S, b0 = blockIdx.x * LB;
-
-  for (int i = tid; i < RW * 6 * 64; i += RT) reinterpret_cast<s8v*>(lds + FwdLds::WX)[i] = wih[i];
-  for (int i = tid; i < 4 * RH; i += RT) {
-    sB[i] = bias4[i];
-    sWq[i] = wq[i];
-  }
-  i8v Wh[3][2][2];
-  int Ws4[3] = {0, 0, 0};
-#pragma unroll
-  for (int g = 0; g < 3; ++g)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int idx = (((wave * 3 + g) * 2 + m) * 2 + ks) * 64 + lane;
-        Wh[g][m][ks] = whh8[idx];
-        Ws4[g] |= (whhs[idx] & 0xFF) << (8 * (2 * m + ks));
-      }
-  const s8v* myWx = reinterpret_cast<const s8v*>(lds + FwdLds::WX) + wave * 6 * 64 + lane;
-  s8v WqA;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int u = 32 * wave + (j < 4 ? 4 * g4 + j : 16 + 4 * g4 + j - 4);
-    WqA[j] = (short)f2bf(l16 < 3 ? wq[l16 * RH + u] : 0.f);
-  }
+  const GruNetW p = online ? args.on : args.tg;   // this block's net
+  float* Qout = online ? args.Q : args.Qt;
+  const int B = args.B, S = args.S, b0 = blockIdx.x * LB;
+#include "gru_weights.h"
   // h0 and x_0
   float hr[2][2][4];
 #pragma unroll
@@ -214,7 +185,7 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd p) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
       const int b = b0 + 16 * n + l16, u0 = 32 * wave + 16 * m + 4 * g4;
-      const float4 v = *reinterpret_cast<const float4*>(p.H0 + (size_t)b * RH + u0);
+      const float4 v = *reinterpret_cast<const float4*>(args.H0 + (size_t)b * RH + u0);
       hr[m][n][0] = v.x; hr[m][n][1] = v.y; hr[m][n][2] = v.z; hr[m][n][3] = v.w;
     }
   if (online) stage_h(sHT + RH * LB, hr);   // block 0 = h0, staged in buffer 1
@@ -224,8 +195,8 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd p) {
   const bool xmover = tid < LB * 4;
   uint4 xnext = {0u, 0u, 0u, 0u};
   if (xmover) {
-    reinterpret_cast<uint4*>(sX + xr * XS)[xc] = reinterpret_cast<const uint4*>(p.X + (size_t)(b0 + xr) * RFL)[xc];
-    xnext = reinterpret_cast<const uint4*>(p.X + ((size_t)B + b0 + xr) * RFL)[xc];
+    reinterpret_cast<uint4*>(sX + xr * XS)[xc] = reinterpret_cast<const uint4*>(args.X + (size_t)(b0 + xr) * RFL)[xc];
+    xnext = reinterpret_cast<const uint4*>(args.X + ((size_t)B + b0 + xr) * RFL)[xc];
   }
   __syncthreads();
   if (online) flush_h(sHT + RH * LB, 0);
@@ -236,83 +207,35 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd p) {
     const bf16_t* cX = sX + cur * LB * XS;
     const unsigned char* cH = sH8 + cur * LB * HS;
     const int* cS = sSc + cur * LB * SCS;
-    float* qp = sQp + cur * RW * 3 * LB;
+    float* sQp = sQp2 + cur * RW * 3 * LB;
     const bool save = online && t < S;
     float keep[2] = {1.f, 1.f};
     if (t < S) {
-      keep[0] = 1.f - p.D[(size_t)t * B + b0 + l16];
-      keep[1] = 1.f - p.D[(size_t)t * B + b0 + 16 + l16];
+      keep[0] = 1.f - args.D[(size_t)t * B + b0 + l16];
+      keep[1] = 1.f - args.D[(size_t)t * B + b0 + 16 + l16];
     }
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
-      f4v ar[2], az[2], anx[2], anh[2];
-#pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        const int u0 = 32 * wave + 16 * m + 4 * g4;
-        ar[m] = *reinterpret_cast<const f4v*>(sB + u0);
-        az[m] = *reinterpret_cast<const f4v*>(sB + RH + u0);
-        anx[m] = *reinterpret_cast<const f4v*>(sB + 2 * RH + u0);
-        anh[m] = *reinterpret_cast<const f4v*>(sB + 3 * RH + u0);
-      }
-      const int row = 16 * n + l16;
-      {
-        const s8v xb = lds_ld8(cX + row * XS + 8 * g4);
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          ar[m] = mfma32(myWx[(0 * 2 + m) * 64], xb, ar[m]);
-          az[m] = mfma32(myWx[(1 * 2 + m) * 64], xb, az[m]);
-          anx[m] = mfma32(myWx[(2 * 2 + m) * 64], xb, anx[m]);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const uint4 h0 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 16 * g4);
-        const uint4 h1 = *reinterpret_cast<const uint4*>(cH + row * HS + 128 * ks + 64 + 16 * g4);
-        i8v hb;
-        hb[0] = (int)h0.x; hb[1] = (int)h0.y; hb[2] = (int)h0.z; hb[3] = (int)h0.w;
-        hb[4] = (int)h1.x; hb[5] = (int)h1.y; hb[6] = (int)h1.z; hb[7] = (int)h1.w;
-        const int sc = cS[row * SCS + 4 * ks + g4];
-#define ST_MX3(M, KS)                                                              \
-  ar[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[0][M][KS], hb, ar[M], Ws4[0], sc);          \
-  az[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[1][M][KS], hb, az[M], Ws4[1], sc);          \
-  anh[M] = mx_mfma_sel<2 * (M) + (KS)>(Wh[2][M][KS], hb, anh[M], Ws4[2], sc);
-        if (ks == 0) { ST_MX3(0, 0) ST_MX3(1, 0) } else { ST_MX3(0, 1) ST_MX3(1, 1) }
-#undef ST_MX3
-      }
+      float (&hrt)[2][2][4] = hr;
       float vr[8], vz[8], vn[8], vg[8], vh[8];
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float r = sigm_ps(ar[m][i]);
-          const float z = sigm_ps(az[m][i]);
-          const float nn = tanh_ps(__builtin_fmaf(r, anh[m][i], anx[m][i]));
-          // gh_n un-scaled for the backward (the packed weights are pre-scaled, gru_common.h)
-          vr[4 * m + i] = r; vz[4 * m + i] = z; vn[4 * m + i] = nn; vg[4 * m + i] = anh[m][i] * (1.f / GS_N);
-          vh[4 * m + i] = hr[m][n][i];
-          hr[m][n][i] = __builtin_fmaf(z, hr[m][n][i] - nn, nn);
-        }
-      if (save) {
-        uint4* sv = p.sv + ((((size_t)t * nblk + blockIdx.x) * RW + wave) * NSV * 2) * 64 + lane;
-        sv[(0 * 2 + n) * 64] = pack8_bf(vr);
-        sv[(1 * 2 + n) * 64] = pack8_bf(vz);
-        sv[(2 * 2 + n) * 64] = pack8_bf(vn);
-        sv[(3 * 2 + n) * 64] = pack8_bf(vg);
-        sv[(4 * 2 + n) * 64] = pack8_bf(vh);
-      }
-      {
-        s8v hb;
-        const uint32_t p0 = pack_bf2(hr[0][n][0], hr[0][n][1]), p1 = pack_bf2(hr[0][n][2], hr[0][n][3]);
-        const uint32_t p2 = pack_bf2(hr[1][n][0], hr[1][n][1]), p3 = pack_bf2(hr[1][n][2], hr[1][n][3]);
-        hb[0] = (short)(p0 & 0xFFFF); hb[1] = (short)(p0 >> 16); hb[2] = (short)(p1 & 0xFFFF); hb[3] = (short)(p1 >> 16);
-        hb[4] = (short)(p2 & 0xFFFF); hb[5] = (short)(p2 >> 16); hb[6] = (short)(p3 & 0xFFFF); hb[7] = (short)(p3 >> 16);
-        const f4v q = mfma32(WqA, hb, zero4());
-        if (g4 == 0) {
-          qp[(wave * 3 + 0) * LB + row] = q[0];
-          qp[(wave * 3 + 1) * LB + row] = q[1];
-          qp[(wave * 3 + 2) * LB + row] = q[2];
-        }
-      }
+      // kept for the backward; gh_n un-scaled (the packed weights are pre-scaled, gru_common.h)
+#define GRU_TILE_STAMP
+#define GRU_TILE_SAVE(m, i, r, z, nn, gh_n, h_prev)                                                        \
+  vr[4 * (m) + (i)] = (r); vz[4 * (m) + (i)] = (z); vn[4 * (m) + (i)] = (nn);                              \
+  vg[4 * (m) + (i)] = (gh_n) * (1.f / GS_N); vh[4 * (m) + (i)] = (h_prev);
+#define GRU_TILE_SAVED                                                                                     \
+  if (save) {                                                                                              \
+    uint4* sv = args.sv + ((((size_t)t * nblk + blockIdx.x) * RW + wave) * NSV * 2) * 64 + lane;           \
+    sv[(0 * 2 + n) * 64] = pack8_bf(vr);                                                                   \
+    sv[(1 * 2 + n) * 64] = pack8_bf(vz);                                                                   \
+    sv[(2 * 2 + n) * 64] = pack8_bf(vn);                                                                   \
+    sv[(3 * 2 + n) * 64] = pack8_bf(vg);                                                                   \
+    sv[(4 * 2 + n) * 64] = pack8_bf(vh);                                                                   \
+  }
+#include "gru_net_tile.h"
+#undef GRU_TILE_SAVED
+#undef GRU_TILE_SAVE
+#undef GRU_TILE_STAMP
     }
     if (t < S) {
 #pragma unroll
@@ -325,18 +248,20 @@ __global__ void __launch_bounds__(RT, 1) gru_seq_fwd_kernel(GruSeqFwd p) {
       quant_h(hr, sH8 + nxt * LB * HS, sSc + nxt * LB * SCS, wave, l16, g4);
       if (xmover) {
         reinterpret_cast<uint4*>(sX + nxt * LB * XS + xr * XS)[xc] = xnext;
-        if (t + 2 <= S) xnext = reinterpret_cast<const uint4*>(p.X + ((size_t)(t + 2) * B + b0 + xr) * RFL)[xc];
+        if (t + 2 <= S) xnext = reinterpret_cast<const uint4*>(args.X + ((size_t)(t + 2) * B + b0 + xr) * RFL)[xc];
       }
     }
     __syncthreads();
     if (online && t + 1 < S) flush_h(sHT + cur * RH * LB, t + 1);
     if (wave == 0 && lane < LB) {
+      // gru_q_row's sum, written out: the call cost the kernel 1.7 % (profiles/gru_learn_shared_bar.md: inlined,
+      // the step loop's MFMA phase is scheduled in another order); like this the kernel is what it was
       float q[3];
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         float v = sWq[3 * RH + a];
 #pragma unroll
-        for (int w = 0; w < RW; ++w) v += qp[(w * 3 + a) * LB + lane];
+        for (int w = 0; w < RW; ++w) v += sQp[(w * 3 + a) * RN + lane];
         q[a] = v;
       }
       *reinterpret_cast<float4*>(Qout + ((size_t)t * B + b0 + lane) * 4) = make_float4(q[0], q[1], q[2], 0.f);

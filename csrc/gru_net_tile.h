@@ -4,15 +4,28 @@
 // accumulators at 32 VGPRs (W_hh holds 108).
 //
 // This is the one definition of the bar's arithmetic, as statements: the two actors (gru.hip), the backtest
-// (gru_rollout.hip) and the server (gru_serve.hip) include it inside their `for (n = 0; n < 2; ++n)` loop.  It is
+// (gru_rollout.hip), the server (gru_serve.hip) and the learner's forward (gru_seq_fwd_kernel, gru_learn.hip), which
+// evaluates the function the actors act with, include it inside their `for (n = 0; n < 2; ++n)` loop.  It is
 // not a function because the same text as a force-inlined function is simplified on its own before it is
 // inlined, and the step loops of the pair actor and the backtest then issued one LDS read of the tile 0 -> 1
 // hand-over later and ran 0.5 to 0.8 % slower (profiles/gru_shared_bar.md); included in place, the loops are the
 // ones the kernels had when each carried a copy.
 // No `#pragma once`: plain statements, included once per kernel.
 // In scope at the point of inclusion: n; Wh, Ws4, myWx, WqA (gru_weights.h); cX / cH / cS, the x rows, the fp8
-// h tile and its scales the step reads; sB, sQp; hrt, a float (&)[2][2][4] on the chunk's h; wave, l16, g4; and
-// the macro GRU_TILE_STAMP: a statement run after the tile's MFMAs (the single actor's debug stamp), or empty.
+// h tile and its scales the step reads; sB, sQp ([RW][3][RN] floats); hrt, a float (&)[2][2][4] on the chunk's h;
+// wave, l16, g4; and the macro GRU_TILE_STAMP: a statement run after the tile's MFMAs (the single actor's debug
+// stamp), or empty.
+// Optional, for the learner, which keeps the gates for its backward (without a definition nothing is kept):
+// GRU_TILE_SAVE(m, i, r, z, nn, gh_n, h_prev), statements run for unit (m, i) once its gates are formed and before
+// its h is overwritten (gh_n is the pre-scaled accumulator), and GRU_TILE_SAVED, a statement run after the tile's
+// GRU update and before its Q MFMA: there the learner stores what it kept.  After the Q partials the same stores
+// cost the learner's forward 4.5 % (profiles/gru_learn_shared_bar.md).
+#ifndef GRU_TILE_SAVE
+#define GRU_TILE_SAVE(m, i, r, z, nn, gh_n, h_prev)
+#endif
+#ifndef GRU_TILE_SAVED
+#define GRU_TILE_SAVED
+#endif
   f4v ar[2], az[2], anx[2], anh[2];   // accumulators start at the biases (b_ir+b_hr, b_iz+b_hz, b_in, b_hn)
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
@@ -56,8 +69,10 @@
       const float r = sigm_ps(ar[m][i]);
       const float z = sigm_ps(az[m][i]);
       const float nn = tanh_ps(__builtin_fmaf(r, anh[m][i], anx[m][i]));
+      GRU_TILE_SAVE(m, i, r, z, nn, anh[m][i], hrt[m][n][i])
       hrt[m][n][i] = __builtin_fmaf(z, hrt[m][n][i] - nn, nn);
     }
+  GRU_TILE_SAVED
   // Q partials of this wave's units: one MFMA, h' (bf16) taken straight from the accumulator layout
   s8v hb;
   const uint32_t p0 = pack_bf2(hrt[0][n][0], hrt[0][n][1]), p1 = pack_bf2(hrt[0][n][2], hrt[0][n][3]);

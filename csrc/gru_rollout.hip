@@ -26,12 +26,7 @@
 namespace st {
 namespace grollout {
 
-struct GruRollout {
-  const i8v* whh8;             // packed weights (GruPack)
-  const int* whhs;
-  const s8v* wih;
-  const float* bias4;
-  const float* wq;
+struct GruRollout : GruNetW {  // the packed weights first (gru_common.h)
   const bf16_t* feat;          // [E][T][RMF]
   const float* close;          // [E][T]
   const float* ret;            // [E][T]
@@ -51,6 +46,7 @@ struct GruRollout {
   float eps, cost, inv_ep_len; // eps = inf: greedy, no draws
   uint32_t key0, key1, env_offset;   // draw counter: (env_offset + e, t, 0, "GRB1")
 };
+ST_FOLLOWS_NETW(GruRollout, feat)
 
 // What the ledger instance writes besides GruRollout's outputs.  {ep_ret, ep_trades, state_out, stats} are given
 // together or not at all, and so are {part, curve}; state_in null = a fresh ledger (zeros).
@@ -339,8 +335,7 @@ namespace {
 // Every reward needs close[t + 1]: start + steps <= T - 1.
 bool rollout_ok(const st::grollout::GruRollout* p) {
   return !(p->E < 1 || p->steps < 1 || p->ep_len < 1 || p->origin > p->start || p->start < 0 ||
-           (long long)p->start + p->steps > (long long)p->T - 1 || p->whh8 == nullptr || p->whhs == nullptr ||
-           p->wih == nullptr || p->bias4 == nullptr || p->wq == nullptr || p->feat == nullptr ||
+           (long long)p->start + p->steps > (long long)p->T - 1 || !st::net_ok(*p) || p->feat == nullptr ||
            p->close == nullptr || p->ret == nullptr || p->out_ret == nullptr || p->out_trades == nullptr ||
            p->out_long == nullptr || p->out_position == nullptr || p->out_entry == nullptr);
 }

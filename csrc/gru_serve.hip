@@ -24,12 +24,7 @@
 namespace st {
 namespace gserve {
 
-struct GruServe {
-  const i8v* whh8;             // packed weights (GruPack)
-  const int* whhs;
-  const s8v* wih;
-  const float* bias4;
-  const float* wq;
+struct GruServe : GruNetW {    // the packed weights first (gru_common.h)
   const int* slot;             // [B]
   const bf16_t* feat;          // [B][RMF]
   const float* close;          // [B]
@@ -44,6 +39,7 @@ struct GruServe {
   float eps, cost, inv_ep_len; // eps = inf: greedy, no draws
   uint32_t key0, key1;
 };
+ST_FOLLOWS_NETW(GruServe, slot)
 
 // the scalar record of a slot, 16 dwords (the first 11 in use)
 constexpr int REC = 16;
@@ -307,9 +303,8 @@ extern "C" int st_gru_serve_lds_bytes() { return st::gserve::Lds::BYTES; }
 // finish the chunks in the same number of rounds (GruPolicy._auto_grid)
 extern "C" hipError_t st_gru_serve_launch(const st::gserve::GruServe* p, int grid, hipStream_t stream) {
   using namespace st::gserve;
-  if (p == nullptr || p->B < 1 || p->S < 1 || p->ep_len < 1 || p->whh8 == nullptr || p->whhs == nullptr ||
-      p->wih == nullptr || p->bias4 == nullptr || p->wq == nullptr || p->slot == nullptr || p->feat == nullptr ||
-      p->close == nullptr || p->h == nullptr || p->rec == nullptr || p->action == nullptr ||
+  if (p == nullptr || p->B < 1 || p->S < 1 || p->ep_len < 1 || !st::net_ok(*p) || p->slot == nullptr ||
+      p->feat == nullptr || p->close == nullptr || p->h == nullptr || p->rec == nullptr || p->action == nullptr ||
       p->position == nullptr || p->reward == nullptr)
     return hipErrorInvalidValue;
   // the dynamic-LDS limit is a per-device attribute of the function: set once on every device launched on

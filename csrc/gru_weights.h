@@ -1,10 +1,11 @@
 // The weight prologue of the GRU(256) policy kernels, as statements: the two actors (gru.hip), the backtest
-// (gru_rollout.hip) and the server (gru_serve.hip) include this once, before their first barrier.  Like
-// gru_net_tile.h it is included in place and is not a function: through force-inlined functions the resident W_hh
-// fragments landed in other registers and the backtest's launch was 1.1 % slower (profiles/gru_shared_bar.md);
-// included, the kernels compile to what they were when each carried a copy.  No `#pragma once`: plain statements.
-// In scope at the point of inclusion: p with the GruPack pointers whh8, whhs, wih, bias4, wq; the LDS carves sWx
-// (const s8v*, RW*6*64 fragments), sB and sWq (float [4*RH] each); tid, lane, l16, g4, wave.
+// (gru_rollout.hip), the server (gru_serve.hip) and the learner's forward (gru_seq_fwd_kernel, gru_learn.hip, on its
+// block's net: online or target) include this once, before their first barrier.  Like gru_net_tile.h it is
+// included in place and is not a function: through force-inlined functions the resident W_hh fragments landed in
+// other registers and the backtest's launch was 1.1 % slower (profiles/gru_shared_bar.md); included, the kernels
+// compile to what they were when each carried a copy.  No `#pragma once`: plain statements.
+// In scope at the point of inclusion: p, a GruNetW (gru_common.h) or a launch struct derived from it; the LDS
+// carves sWx (const s8v*, RW*6*64 fragments), sB and sWq (float [4*RH] each); tid, lane, l16, g4, wave.
 // Declares: Wh, Ws4, myWx, WqA.  A workgroup barrier must follow before the staged LDS data is read.
 
   // W_ih fragments, the gate biases and W_q rows + b_q into LDS, by every thread

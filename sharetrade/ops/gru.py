@@ -44,9 +44,25 @@ class PackArgs(C.Structure):
                 ("whhTs", C.c_void_p)]
 
 
+NETW_NAMES = ("whh8", "whhs", "wih", "bias4", "wq")
+
+
+class NetW(C.Structure):
+    """``GruNetW`` of ``csrc/gru_common.h``: the packed weights of one net (``st_gru_pack``'s outputs).  The launch
+    structs of the actors, the backtest and the server start with one, anonymous: ``a.whh8`` reads and writes it."""
+    _fields_ = [(n, C.c_void_p) for n in NETW_NAMES]
+
+
+def set_netw(w, packed) -> None:
+    """Point a :class:`NetW`, a launch struct that starts with one, or the outputs of a :class:`PackArgs` at a
+    dict of packed tensors."""
+    for n in NETW_NAMES:
+        setattr(w, n, packed[n].data_ptr())
+
+
 class ActArgs(C.Structure):
-    _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
-                ("wq", C.c_void_p), ("feat", C.c_void_p), ("close", C.c_void_p), ("ret", C.c_void_p),
+    _anonymous_ = ("net",)
+    _fields_ = [("net", NetW), ("feat", C.c_void_p), ("close", C.c_void_p), ("ret", C.c_void_p),
                 ("E", C.c_int), ("T", C.c_int), ("S", C.c_int), ("ep_len", C.c_int),
                 ("eps", C.c_float), ("inv_ramp", C.c_float), ("cost", C.c_float), ("inv_ep_len", C.c_float),
                 ("h", C.c_void_p), ("pos", C.c_void_p), ("ep_start", C.c_void_p), ("position", C.c_void_p),
@@ -59,8 +75,8 @@ class ActArgs(C.Structure):
 
 class RolloutArgs(C.Structure):
     """``GruRollout`` of ``csrc/gru_rollout.hip``: a frozen policy over bars start .. start + steps - 1."""
-    _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
-                ("wq", C.c_void_p), ("feat", C.c_void_p), ("close", C.c_void_p), ("ret", C.c_void_p),
+    _anonymous_ = ("net",)
+    _fields_ = [("net", NetW), ("feat", C.c_void_p), ("close", C.c_void_p), ("ret", C.c_void_p),
                 ("h0", C.c_void_p), ("position", C.c_void_p), ("entry", C.c_void_p),
                 ("out_ret", C.c_void_p), ("out_trades", C.c_void_p), ("out_long", C.c_void_p),
                 ("out_position", C.c_void_p), ("out_entry", C.c_void_p), ("out_h", C.c_void_p),
@@ -93,8 +109,8 @@ LEDGER_STATS_FLOAT = frozenset({"max_dd", "sumsq", "win_sum", "loss_sum"})
 
 class ServeArgs(C.Structure):
     """``GruServe`` of ``csrc/gru_serve.hip``: B request rows, one bar each, on a table of S session slots."""
-    _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
-                ("wq", C.c_void_p), ("slot", C.c_void_p), ("feat", C.c_void_p), ("close", C.c_void_p),
+    _anonymous_ = ("net",)
+    _fields_ = [("net", NetW), ("slot", C.c_void_p), ("feat", C.c_void_p), ("close", C.c_void_p),
                 ("flags", C.c_void_p), ("h", C.c_void_p), ("rec", C.c_void_p), ("action", C.c_void_p),
                 ("position", C.c_void_p), ("reward", C.c_void_p), ("q", C.c_void_p),
                 ("B", C.c_int), ("S", C.c_int), ("ep_len", C.c_int), ("eps", C.c_float), ("cost", C.c_float),
@@ -119,11 +135,6 @@ class GatherArgs(C.Structure):
                 ("rctrl", C.c_void_p), ("cap", C.c_int), ("S", C.c_int), ("B", C.c_int), ("key0", C.c_uint32),
                 ("key1", C.c_uint32), ("step", C.c_void_p), ("X", C.c_void_p), ("H0", C.c_void_p),
                 ("A", C.c_void_p), ("R", C.c_void_p), ("D", C.c_void_p)]
-
-
-class NetW(C.Structure):
-    _fields_ = [("whh8", C.c_void_p), ("whhs", C.c_void_p), ("wih", C.c_void_p), ("bias4", C.c_void_p),
-                ("wq", C.c_void_p)]
 
 
 class SeqFwdArgs(C.Structure):

@@ -600,8 +600,7 @@ class GruPolicy:
             p = G.PackArgs()
             for n in PARAM_NAMES:
                 setattr(p, n, self.params[n].data_ptr())
-            for n, t in pk.items():
-                setattr(p, n, t.data_ptr())
+            G.set_netw(p, pk)
             p.whhT8, p.whhTs = None, None
             native.check(G.lib().st_gru_pack(p, native.stream_handle()), "st_gru_pack")
         self.packed = pk
@@ -710,8 +709,7 @@ class GruPolicy:
                 out["reward"] = torch.empty(E, steps, device=dev)
             args = G.RolloutLedgerArgs() if ledger else G.RolloutArgs()
             a = args.r if ledger else args
-            for n, t in self.packed.items():
-                setattr(a, n, t.data_ptr())
+            G.set_netw(a, self.packed)
             a.feat, a.close, a.ret = feat.data_ptr(), close.data_ptr(), ret.data_ptr()
             a.h0, a.position, a.entry = native.ptr(h0), native.ptr(position), native.ptr(entry)
             a.out_ret, a.out_trades, a.out_long = (out[k].data_ptr() for k in ("ret", "trades", "long"))

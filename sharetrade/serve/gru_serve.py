@@ -478,8 +478,7 @@ class GruSessionServer:
         from ..ops import native
 
         a = G.ServeArgs()
-        for n, t in self.policy.packed.items():
-            setattr(a, n, t.data_ptr())
+        G.set_netw(a, self.policy.packed)
         a.slot, a.feat, a.close, a.flags = slots.data_ptr(), feat.data_ptr(), close.data_ptr(), native.ptr(flags)
         a.h, a.rec = self.table["h"].data_ptr(), self.table["rec"].data_ptr()
         a.action, a.position, a.reward, a.q = (actions.data_ptr(), position.data_ptr(), reward.data_ptr(),

@@ -248,7 +248,7 @@ class RecurrentDQN:
         for par in (0, 1):
             a = G.ActArgs()
             po = self._on(par)
-            a.whh8, a.whhs, a.wih, a.bias4, a.wq = (po[k].data_ptr() for k in ("whh8", "whhs", "wih", "bias4", "wq"))
+            G.set_netw(a, po)
             a.feat, a.close, a.ret = self.feat.data_ptr(), self.close.data_ptr(), self.ret.data_ptr()
             a.E, a.T, a.S, a.ep_len = self.E, self.T, self.S, self.ep_len
             ag = self.cfg.agent
@@ -269,7 +269,7 @@ class RecurrentDQN:
             p.w_hh, p.w_ih, p.b_ih, p.b_hh, p.w_q, p.b_q = (src[n].data_ptr() for n in
                                                              ("w_hh", "w_ih", "b_ih", "b_hh", "w_q", "b_q"))
             pk = self.pk[net] if net == "tg" else self._on(int(net[-1]))
-            p.whh8, p.whhs, p.wih, p.bias4, p.wq = (pk[k].data_ptr() for k in ("whh8", "whhs", "wih", "bias4", "wq"))
+            G.set_netw(p, pk)
             if "whhT8" in pk:
                 p.whhT8, p.whhTs = pk["whhT8"].data_ptr(), pk["whhTs"].data_ptr()
             self._packs[net] = p
@@ -285,8 +285,7 @@ class RecurrentDQN:
         for par in (0, 1):
             f = G.SeqFwdArgs()
             for pk, w in ((self._on(par), f.on), (self.pk["tg"], f.tg)):
-                w.whh8, w.whhs, w.wih, w.bias4, w.wq = (pk[k].data_ptr() for k in ("whh8", "whhs", "wih", "bias4",
-                                                                                  "wq"))
+                G.set_netw(w, pk)
             f.X, f.H0, f.D = self.X.data_ptr(), self.H0.data_ptr(), self.D.data_ptr()
             f.Q, f.Qt, f.sv = self.Q.data_ptr(), self.Q_t.data_ptr(), self.sv.data_ptr()
             f.HT, f.ldht = self.HT.data_ptr(), int(self.HT.stride(0))

@@ -69,3 +69,18 @@ def test_fused_step_params_are_the_whole_mirror(lib_available):
     from sharetrade.ops.native import QStepParams
 
     assert _sizes("st_abi_qstep_fused") == [C.sizeof(QStepParams)]
+
+
+def test_gru_launch_structs_start_with_the_packed_weights():
+    """ActArgs, RolloutArgs and ServeArgs carry the net as an anonymous NetW: its five pointers read and write as
+    members of the struct itself, at the offsets they had when each struct spelled them out."""
+    from sharetrade.ops import gru as G
+
+    for cls, first in ((G.ActArgs, "feat"), (G.RolloutArgs, "feat"), (G.ServeArgs, "slot")):
+        for i, n in enumerate(G.NETW_NAMES):
+            assert getattr(cls, n).offset == 8 * i and getattr(cls, n).size == 8, (cls.__name__, n)
+        assert getattr(cls, first).offset == C.sizeof(G.NetW) == 40, cls.__name__
+        a = cls()
+        a.whh8, a.wq = 0x1000, None
+        assert a.net.whh8 == 0x1000 and a.net.wq is None and a.whh8 == 0x1000
+    assert C.sizeof(G.RolloutArgs) == 20 * 8 + 12 * 4

@@ -81,11 +81,6 @@ def _packed(seed: int, heavy: bool = False) -> dict:
     return out
 
 
-def _netw(w, pk):
-    b = pk["b"]
-    w.whh8, w.whhs, w.wih, w.bias4, w.wq = (b[n].ptr() for n in ("whh8", "whhs", "wih", "bias4", "wq"))
-
-
 # ----------------------------------------------------------------------------- 1. gather
 @pytest.mark.parametrize("S", R.GATHER_S)
 def test_gather(native_built, S):
@@ -177,7 +172,8 @@ def _fwd_launch(G, k, inp, on, tg, B, S, pad=8):
              Q=_out((S + 1) * B * 4, torch.float32, F_SENT), Qt=_out((S + 1) * B * 4, torch.float32, F_SENT),
              HT=_out((RH + 64) * ldht, torch.bfloat16, BF_SENT), sv=_out(R.sv_size(S, B) // 2, torch.int32, I_SENT))
     f = G.SeqFwdArgs()
-    _netw(f.on, on), _netw(f.tg, tg)
+    for w, pk in ((f.on, on), (f.tg, tg)):
+        G.set_netw(w, {n: band.v for n, band in pk["b"].items()})
     f.X, f.H0, f.D, f.Q, f.Qt, f.HT, f.ldht, f.sv, f.B, f.S = (b["X"].ptr(), b["H0"].ptr(), b["D"].ptr(), b["Q"].ptr(),
                                                                  b["Qt"].ptr(), b["HT"].ptr(), ldht, b["sv"].ptr(), B, S)
     before = b.snap()
@@ -251,7 +247,8 @@ def test_forward_rejections(native_built):
                  Q=_out(2 * 96 * 4, torch.float32, F_SENT), HT=_out((RH + 64) * 2 * 96, torch.bfloat16, BF_SENT),
                  sv=_out(R.sv_size(1, 96) // 2, torch.int32, I_SENT))
         f = G.SeqFwdArgs()
-        _netw(f.on, on), _netw(f.tg, tg)
+        for w, pk in ((f.on, on), (f.tg, tg)):
+            G.set_netw(w, {n: band.v for n, band in pk["b"].items()})
         f.X, f.H0, f.D, f.Q, f.Qt, f.HT, f.ldht, f.sv, f.B, f.S = (b["X"].ptr(), b["H0"].ptr(), b["D"].ptr(), b["Q"].ptr(),
                                                                      b["Q"].ptr(), b["HT"].ptr(), 2 * 96, b["sv"].ptr(), B, S)
         before = b.snap()
