@@ -4,6 +4,9 @@ The oracle (`sharetrade.env.trading.engine_step_ref`) rounds to bf16 at the same
 points as the kernel (``emulate_bf16=True``); accumulation order differs, so
 gradients are compared with a relative-norm tolerance while env transitions
 (fp32, no FMA contraction on either side) must match exactly.
+
+These are whole-layer norms.  tests/test_gpu_step_exact.py compares the same kernels bit for bit with a float64
+model on inputs whose sums are exact in fp32 (tests/step_refs.py; figures in profiles/step_refs.md).
 """
 import numpy as np
 import pytest

@@ -6,6 +6,10 @@ The oracle (`sharetrade.env.trading.engine_step_ref`) rounds to bf16 at the same
 MFMAs differs); with the kernel's actions forced into the oracle, env transitions and rewards must match
 exactly and the gradient within a relative-norm tolerance.  Small ``engine.grid`` values make every
 workgroup run many tiles, so the LDS ring of the kernel wraps around many times.
+
+These are whole-layer norms and action-mismatch rates.  tests/test_gpu_step_exact.py compares the kernel bit for bit
+with a float64 model -- actions, state, every slab row, the reduced gradient, the statistics row -- on inputs whose
+sums are exact in fp32 (tests/step_refs.py; figures in profiles/step_refs.md); it reuses KERNELS and _cfg from here.
 """
 import os
 

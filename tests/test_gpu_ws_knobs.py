@@ -10,6 +10,9 @@ plain-PyTorch oracle (sharetrade.env.trading.engine_step_ref):
 
 The reference's agent has none of these (QDecisionPolicyActor.scala:58-71 is the online one-step DQN); they
 are the experiments of docs/LEARNING.md, here at the flagship kernel's speed.
+
+The QT buffer and the knob build are also compared bit for bit with a float64 model on exact inputs
+(tests/test_gpu_step_exact.py::test_ws_knob_build_and_target_pass_exact).
 """
 import numpy as np
 import pytest
