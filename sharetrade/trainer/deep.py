@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import weakref
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -26,14 +27,9 @@ from ..config import Config
 from ..ops import gemm as gm
 from ..ops import native
 from ..utils import rng
+from .graphs import IterationDriver, driver_attr, driver_graph
 
 ACT_PAD = 64  # output layer rows padded to a GEMM tile
-
-
-# HIP-graph capture mode: "thread_local" -- with an RCCL process group alive, its watchdog thread
-# polls collective events during our captures; in the default global mode that poll invalidates the
-# capture (hipErrorStreamCaptureInvalidated) and kills the watchdog.  Our own thread stays checked.
-_CAPTURE_MODE = "thread_local"
 
 
 class _Replay(C.Structure):
@@ -242,9 +238,9 @@ class DeepDQN:
             self.Wt.append(self.Wb[l].clone())
             self.bt.append(self.b[l].clone())
         # weight + bias gradients: views of one flat fp32 buffer (dW first: the replay gather zeroes
-        # the split-K span; the whole buffer is the data-parallel all-reduce bucket)
+        # the split-K span; the whole buffer is the data-parallel all-reduce bucket, ``grad_bucket``)
         sizes = [self.pdims[l + 1] * self.pdims[l] for l in range(self.L)]
-        self.grad_flat = torch.zeros(sum(sizes) + sum(self.pdims[1:]), device=dev)
+        self.grad_flat = self.grad_bucket = torch.zeros(sum(sizes) + sum(self.pdims[1:]), device=dev)
         self._dW_flat = self.grad_flat[:sum(sizes)]
         off = 0
         for l in range(self.L):
@@ -360,10 +356,14 @@ class DeepDQN:
         self.Acte = [None] + [torch.zeros(self.E, h, dtype=b16, device=dev) for h in hid]
         self.Qe = torch.zeros(self.E, ACT_PAD, device=dev)
         self.key0, self.key1 = (int(x) for x in rng.key_for(self.seed, 0))
-        self.updates = 0
-        self.env_steps = 0
-        self._g_act = None
-        self._g_upd = None
+        # the graph-replay driver (graphs.py); its hooks reach the learner over a weak proxy: no reference cycle
+        me = weakref.proxy(self)
+        self._drv = IterationDriver(
+            act=lambda: me.act_step(), update=lambda with_act, flip: me.update_step(with_act),
+            grads=lambda with_act: me.update_step(with_act, split=True), apply=lambda: me._adam_step(),
+            sync_target=lambda: me.sync_target(), sync_bucket=lambda: me.grad_sync(me.grad_bucket),
+            whole_graph=lambda: me.grad_sync is None or me.capture_sync,
+            target_every=lambda: me.target_every, overlap_act=self.overlap_act, device=dev)
         self._build_structs()
 
     # ---------------------------------------------------------------- ctypes structs
@@ -726,110 +726,25 @@ class DeepDQN:
             self.Wt[l].copy_(self.Wb[l])
             self.bt[l].copy_(self.b[l])
 
-    # ---------------------------------------------------------------- driver
+    # ---------------------------------------------------------------- driver (trainer/graphs.py)
+    updates, env_steps, _captured = driver_attr("updates"), driver_attr("acts"), driver_attr("captured")
+    _g_act, _g_upd, _g_iter, _g_iter_k = (driver_graph(k) for k in ("act", "upd", "iter", "iter_k"))
+    _g_pre, _g_pre_act = driver_graph("pre"), driver_graph("pre_act")
+
     def capture(self, iters_per_graph: int = 1) -> None:
         """Capture one act step and one update into HIP graphs (after a warm-up of each).  With
         ``iters_per_graph`` k > 1 (overlapped single-update iterations without a host all-reduce) also k whole
         iterations into one graph, which ``iterations(n)`` replays: one graph launch per k iterations instead
         of per iteration."""
-        s = torch.cuda.Stream(self.dev)
-        s.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(s):
-            if self.overlap_act:
-                self.update_step(with_act=True)   # same op order as the captured iteration
-            else:
-                self.act_step()
-                self.update_step()
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        self.env_steps += 1
-        self.updates += 1
-        if self.target_every and self.updates % self.target_every == 0:   # as iteration()
-            self.sync_target()
-        self._g_act = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._g_act, capture_error_mode=_CAPTURE_MODE):
-            self.act_step()
-        self._g_upd = self._g_iter = self._g_pre = self._g_pre_act = self._g_post = None
-        if self.grad_sync is None or self.capture_sync:
-            self._g_upd = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_upd, capture_error_mode=_CAPTURE_MODE):
-                self.update_step()
-            if self.overlap_act:
-                self._g_iter = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g_iter, capture_error_mode=_CAPTURE_MODE):
-                    self.update_step(with_act=True)
-                if iters_per_graph > 1:
-                    self._g_iter_k = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._g_iter_k, capture_error_mode=_CAPTURE_MODE):
-                        for _ in range(iters_per_graph):
-                            self.update_step(with_act=True)
-                    self._iter_k = int(iters_per_graph)
-        else:
-            # data parallel: the gradient all-reduce runs between two graphs (act + gradients | Adam);
-            # the collective itself stays outside the capture
-            self._g_pre = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_pre, capture_error_mode=_CAPTURE_MODE):
-                self.update_step(split=True)
-            if self.overlap_act:
-                self._g_pre_act = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g_pre_act, capture_error_mode=_CAPTURE_MODE):
-                    self.update_step(with_act=True, split=True)
-            self._g_post = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_post, capture_error_mode=_CAPTURE_MODE):
-                self._adam_step()
-        self._captured = True
-
-    def _replay_dp(self, with_act: bool) -> None:
-        (self._g_pre_act if with_act else self._g_pre).replay()
-        self.grad_sync(self.grad_flat)
-        self._g_post.replay()
+        self._drv.capture(iters_per_graph)
 
     def iterations(self, n: int) -> None:
         """n single-update iterations: whole k-iteration graphs (``capture(iters_per_graph=k)``) where the
         target-net copy cannot fall inside one (it runs on the host between graphs), single ones otherwise."""
-        k = getattr(self, "_iter_k", 1)
-        g = getattr(self, "_g_iter_k", None)
-        while n > 0:
-            if (g is not None and n >= k and (not self.target_every or
-                                              self.updates // self.target_every == (self.updates + k - 1) // self.target_every)):
-                g.replay()
-                self.env_steps += k
-                self.updates += k
-                if self.target_every and self.updates % self.target_every == 0:
-                    self.sync_target()
-                n -= k
-            else:
-                self.iteration()
-                n -= 1
+        self._drv.iterations(n)
 
     def iteration(self, updates_per_step: int = 1) -> None:
-        if self.overlap_act and updates_per_step >= 1:
-            if getattr(self, "_g_pre_act", None) is not None:
-                self._replay_dp(True)
-            elif getattr(self, "_g_iter", None) is not None:
-                self._g_iter.replay()
-            else:
-                self.update_step(with_act=True)
-            self.env_steps += 1
-            self.updates += 1
-            if self.target_every and self.updates % self.target_every == 0:
-                self.sync_target()
-            updates_per_step -= 1
-        else:
-            if self._g_act is not None:
-                self._g_act.replay()
-            else:
-                self.act_step()
-            self.env_steps += 1
-        for _ in range(updates_per_step):
-            if getattr(self, "_g_pre", None) is not None:
-                self._replay_dp(False)
-            elif self._g_upd is not None:
-                self._g_upd.replay()
-            else:
-                self.update_step()
-            self.updates += 1
-            if self.target_every and self.updates % self.target_every == 0:
-                self.sync_target()
+        self._drv.iteration(updates_per_step)
 
     # ---------------------------------------------------------------- checkpoint / resume
     _ENV_KEYS = ("budget", "shares", "value", "pos", "episodes", "last_final", "env_ctrl", "rp_ctrl", "t_ctr",

@@ -37,16 +37,11 @@ from ..env import trading as tr
 from ..models import qnet as qn
 from ..ops import native
 from ..utils import rng
+from .graphs import CAPTURE_MODE
 
 NSTAT = 8
 STAT_NAMES = ("reward_sum", "loss_sum", "explore", "episodes_done", "final_sum", "final_sq", "qslot_sum", "_")
 OPT_KIND = {"sgd": 0, "adagrad": 1, "adam": 2}
-
-
-# HIP-graph capture mode: "thread_local" -- with an RCCL process group alive, its watchdog thread
-# polls collective events during our captures; in the default global mode that poll invalidates the
-# capture (hipErrorStreamCaptureInvalidated) and kills the watchdog.  Our own thread stays checked.
-_CAPTURE_MODE = "thread_local"
 
 
 def resolve_device(spec: str) -> torch.device:
@@ -778,14 +773,14 @@ class VectorEngine:
                 self.step_count += 1
         torch.cuda.current_stream(self.device).wait_stream(s)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
             self._native_step()
         self._graph = g
         k = int(self.cfg.engine.graph_steps if graph_steps is None else graph_steps)
         self._graph_k = None
         if k > 1:
             gk = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gk, capture_error_mode=_CAPTURE_MODE):
+            with torch.cuda.graph(gk, capture_error_mode=CAPTURE_MODE):
                 for _ in range(k):
                     self._native_step()
             self._graph_k = (gk, k)
@@ -811,9 +806,9 @@ class VectorEngine:
                 self.step_count += 1
         torch.cuda.current_stream(self.device).wait_stream(s)
         pre, post = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(pre, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(pre, capture_error_mode=CAPTURE_MODE):
             self._dp_pre()
-        with torch.cuda.graph(post, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(post, capture_error_mode=CAPTURE_MODE):
             self._dp_post()
         self._graph = _SplitStepGraph(pre, post, self._sync.all_reduce, self.grad)
         self._graph_k = None

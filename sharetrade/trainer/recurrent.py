@@ -24,6 +24,7 @@ x_t = 8 market features ++ (position, unrealised pnl %, elapsed fraction, 1) zer
 from __future__ import annotations
 
 import math
+import weakref
 from typing import Dict, Optional
 
 import numpy as np
@@ -37,14 +38,9 @@ from ..ops import gru as G
 from ..ops import native
 from ..utils import rng
 from .deep import _bind as _bind_deep
+from .graphs import IterationDriver, driver_attr, driver_graph
 
 HID, GATES, XA, XL = G.HID, G.GATES, G.XA, G.XL
-
-
-# HIP-graph capture mode: "thread_local" -- with an RCCL process group alive, its watchdog thread
-# polls collective events during our captures; in the default global mode that poll invalidates the
-# capture (hipErrorStreamCaptureInvalidated) and kills the watchdog.  Our own thread stays checked.
-_CAPTURE_MODE = "thread_local"
 
 
 class RecurrentDQN:
@@ -113,7 +109,7 @@ class RecurrentDQN:
         self.n_params = sum(sizes)
         npad = (self.n_params + 3) // 4 * 4          # float4 columns of the flat Adam kernel; tail stays 0
         self.flat = torch.zeros(npad, device=dev)
-        self.gflat = torch.zeros(npad, device=dev)
+        self.gflat = self.grad_bucket = torch.zeros(npad, device=dev)   # (the data-parallel all-reduce bucket)
         self.mflat = torch.zeros(npad, device=dev)
         self.vflat = torch.zeros(npad, device=dev)
         self.ones = torch.ones(npad, device=dev)
@@ -153,7 +149,14 @@ class RecurrentDQN:
         # while the actor still reads this one, so the re-pack need not wait for the actor (the sets
         # alternate: ``_par`` is the set holding the current weights)
         self.pk["on1"] = {k: torch.zeros_like(v) for k, v in self.pk["on"].items()}
-        self._par = 0
+        # the graph-replay driver (graphs.py); its hooks reach the learner over a weak proxy: no reference cycle
+        me = weakref.proxy(self)
+        self._drv = IterationDriver(
+            act=lambda: me.act(), update=lambda with_act, flip: me.update(with_act, flip),
+            grads=lambda with_act: me._grads(with_act, join=with_act), apply=lambda: me._apply(),
+            sync_target=lambda: me.sync_target(), sync_bucket=lambda: me.grad_sync(me.grad_bucket),
+            whole_graph=lambda: me.grad_sync is None or me.capture_sync,
+            target_every=lambda: me.target_every, overlap_act=self.overlap_act, n_sets=2, device=dev)
         # ---------------------------------------------------------------- data + envs
         # bank: (close fp32 [envs, bars], feat bf16 [envs, bars, 8]) on the device, e.g. windows of real bars
         # (data.ohlcv.window_bank); default: the synthetic generator's bars of this seed
@@ -217,10 +220,6 @@ class RecurrentDQN:
         self.dGxT = torch.zeros(GATES, RS, dtype=b16, device=dev)
         self.dGhT = torch.zeros(GATES, RS, dtype=b16, device=dev)
         self.key0, self.key1 = (int(x) for x in rng.key_for(self.seed, 7))
-        self.updates = 0
-        self.launches = 0
-        self._g_act = self._g_upd = self._g_iter = None
-        self._g_acts, self._g_upds, self._g_iters = {}, {}, {}
         self._build_structs()
         self.pack("on", into=0)
         self.pack("on", into=1)
@@ -434,139 +433,34 @@ class RecurrentDQN:
         self.tflat.copy_(self.flat)
         self.pack("tg")
 
-    # ---------------------------------------------------------------- driver
-    def _flips(self) -> bool:
-        """Whether the overlapped iteration alternates the online sets (not in the split DP capture)."""
-        return self.grad_sync is None or self.capture_sync
+    # ---------------------------------------------------------------- driver (trainer/graphs.py)
+    # (``_par``: the online set holding the current weights)
+    updates, launches, _captured, _par = (driver_attr(n) for n in ("updates", "acts", "captured", "par"))
+    _g_act, _g_upd, _g_iter, _g_iter_k = (driver_graph(k) for k in ("act", "upd", "iter", "iter_k"))
+    _g_pre, _g_pre_act = driver_graph("pre"), driver_graph("pre_act")
 
     def capture(self, iters_per_graph: int = 1) -> None:
         """Warm up, then capture the actor launch, the learner update and (overlap_act) the whole
         iteration into HIP graphs -- one of each per online weight set.  ``iters_per_graph`` k > 1 (even;
         overlapped, alternating sets, no host all-reduce): also k whole iterations per graph, one per
         starting set, which ``iterations(n)`` replays."""
-        s = torch.cuda.Stream(self.dev)
-        s.wait_stream(torch.cuda.current_stream(self.dev))
-        flip = self.overlap_act and self._flips()
-        with torch.cuda.stream(s):
-            if self.overlap_act:
-                self.update(with_act=True, flip=flip)   # same op order as the captured iteration
-            else:
-                self.act()
-                self.update()
-        torch.cuda.current_stream(self.dev).wait_stream(s)
-        if flip:
-            self._par ^= 1
-        self.launches += 1
-        self.updates += 1
-        if self.updates % self.target_every == 0:   # the warm-up is a full iteration (as iteration())
-            self.sync_target()
-        cur = self._par
-        self._g_acts, self._g_upds, self._g_iters = {}, {}, {}
-        self._g_pre = self._g_pre_act = self._g_post = None
-        for par in (0, 1):
-            self._par = par
-            self._g_acts[par] = g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                self.act()
-            if self._flips():
-                self._g_upds[par] = g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                    self.update()
-                if self.overlap_act:
-                    self._g_iters[par] = g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                        self.update(with_act=True, flip=True)
-        self._g_iters_k, self._iter_k = {}, 1
-        if self.overlap_act and self._flips() and iters_per_graph > 1:
-            if iters_per_graph % 2:
-                raise ValueError("iters_per_graph must be even (the online sets alternate)")
-            for par in (0, 1):
-                self._par = par
-                self._g_iters_k[par] = g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-                    for _ in range(iters_per_graph):
-                        self.update(with_act=True, flip=True)
-                        self._par ^= 1
-            self._iter_k = int(iters_per_graph)
-        self._par = cur
-        if not self._flips():
-            # data parallel: the gradient all-reduce runs between two graphs (gradients | Adam + re-pack),
-            # the collective itself stays outside the capture; the actor joins at the end of the first
-            # (the online set never alternates here)
-            self._g_pre = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_pre, capture_error_mode=_CAPTURE_MODE):
-                self._grads()
-            if self.overlap_act:
-                self._g_pre_act = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._g_pre_act, capture_error_mode=_CAPTURE_MODE):
-                    self._grads(with_act=True, join=True)
-            self._g_post = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g_post, capture_error_mode=_CAPTURE_MODE):
-                self._apply()
-        self._g_act, self._g_upd, self._g_iter = (self._g_acts.get(0), self._g_upds.get(0), self._g_iters.get(0))
-        self._captured = True
-
-    def _replay_dp(self, with_act: bool) -> None:
-        (self._g_pre_act if with_act else self._g_pre).replay()
-        self.grad_sync(self.gflat)
-        self._g_post.replay()
+        self._drv.capture(iters_per_graph)
 
     def act_step(self) -> None:
-        g = self._g_acts.get(self._par)
-        if g is not None:
-            g.replay()
-        else:
-            self.act()
-        self.launches += 1
+        """One counted actor launch (its graph once captured)."""
+        self._drv.act_step()
 
     def update_step(self) -> None:
-        if getattr(self, "_g_pre", None) is not None:
-            self._replay_dp(False)
-        elif self._g_upds.get(self._par) is not None:
-            self._g_upds[self._par].replay()
-        else:
-            self.update()
-        self.updates += 1
-        if self.updates % self.target_every == 0:
-            self.sync_target()
+        """One counted update (its graph or graph pair once captured)."""
+        self._drv.update_step()
 
     def iterations(self, n: int) -> None:
         """n single-update iterations: whole k-iteration graphs (``capture(iters_per_graph=k)``) where no
         target-net copy falls inside one (it runs on the host between graphs), single ones otherwise."""
-        k = getattr(self, "_iter_k", 1)
-        gs = getattr(self, "_g_iters_k", {})
-        while n > 0:
-            if gs and n >= k and self.updates // self.target_every == (self.updates + k - 1) // self.target_every:
-                gs[self._par].replay()   # k even: the set alternates back
-                self.launches += k
-                self.updates += k
-                if self.updates % self.target_every == 0:
-                    self.sync_target()
-                n -= k
-            else:
-                self.iteration()
-                n -= 1
+        self._drv.iterations(n)
 
     def iteration(self, updates: int = 1) -> None:
-        if self.overlap_act and updates >= 1:
-            if getattr(self, "_g_pre_act", None) is not None:
-                self._replay_dp(True)
-            elif self._g_iters.get(self._par) is not None:
-                self._g_iters[self._par].replay()
-                self._par ^= 1
-            else:
-                self.update(with_act=True, flip=self._flips())
-                if self._flips():
-                    self._par ^= 1
-            self.launches += 1
-            self.updates += 1
-            if self.updates % self.target_every == 0:
-                self.sync_target()
-            updates -= 1
-        else:
-            self.act_step()
-        for _ in range(updates):
-            self.update_step()
+        self._drv.iteration(updates)
 
     # ---------------------------------------------------------------- held-out evaluation
     def backtest(self, close: Optional[torch.Tensor] = None, feat: Optional[torch.Tensor] = None, *,

@@ -98,8 +98,7 @@ def run(kind: str, cfg: Config, iterations: int, device: Optional[torch.device] 
             raise ValueError(f"learner built for world_size={d.world_size}, the group has {ctx.world_size}")
         from ..parallel.dist import GradSync
 
-        gflat = d.grad_flat if kind == "deep" else d.gflat
-        d.grad_sync = GradSync(ctx, gflat.numel(), bucket_mb=bucket_mb).all_reduce
+        d.grad_sync = GradSync(ctx, d.grad_bucket.numel(), bucket_mb=bucket_mb).all_reduce
         if ctx.backend == "nccl" and capture_sync:
             # RCCL collectives capture into HIP graphs: keep the all-reduce inside the update graph
             # (config 4: per layer on a comm stream, overlapped with the rest of the backward)

@@ -26,7 +26,7 @@ class _Learner:
     def __init__(self, rank, world):
         self.world_size, self.rank = world, rank
         self.flat = torch.full((8,), float(10 * (rank + 1)))     # ranks start apart
-        self.gflat = torch.zeros(8)
+        self.gflat = self.grad_bucket = torch.zeros(8)       # the learners' name for the all-reduce bucket
         self.grad_sync = None
         self.updates = 0
 

@@ -13,7 +13,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sharetrade.config import preset_config  # noqa: E402
-from sharetrade.trainer.engine import _CAPTURE_MODE, VectorEngine  # noqa: E402
+from sharetrade.trainer.engine import VectorEngine  # noqa: E402
+from sharetrade.trainer.graphs import CAPTURE_MODE  # noqa: E402
 
 
 def capture(eng, k):
@@ -21,7 +22,7 @@ def capture(eng, k):
     s.wait_stream(torch.cuda.current_stream(eng.device))
     g = torch.cuda.CUDAGraph()
     with torch.cuda.stream(s):
-        with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+        with torch.cuda.graph(g, capture_error_mode=CAPTURE_MODE):
             for _ in range(k):
                 eng._native_step()
     torch.cuda.current_stream(eng.device).wait_stream(s)
