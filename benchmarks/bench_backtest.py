@@ -8,6 +8,11 @@
   ``torch.cat`` of request rows and the env transition in torch per day);
 * ``serve_rollout``: the same policy through ``PolicyServer.backtest`` (what ``serve_eval.py --rollout`` runs).
 
+``--ledger`` adds, on the bank and shape of ``rollout``: ``rollout_ledger`` (the kernel's ledger instance with the
+portfolio curve, no trace), ``trace_only`` (``trace=True``) and ``trace_then_ledger`` (``trace=True``, then
+``ledger_from_trace`` on the device tensors: the path the ledger launch replaces), and asserts that the ledger
+launch's final portfolios equal the plain launch's bit for bit.
+
 Every run is warm (one untimed repeat first) and timed with HIP events around the whole episode; reported are
 the median, min and max over ``--repeats`` and env-days/s from the median.
 
@@ -56,6 +61,8 @@ def main() -> int:
     ap.add_argument("--length", type=int, default=None, help="days per series (default: data.length of the preset)")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--what", default="rollout,greedy,loop,serve_rollout")
+    ap.add_argument("--ledger", action="store_true",
+                    help="with rollout: also time rollout_ledger, trace_only and trace_then_ledger")
     args = ap.parse_args()
     what = set(args.what.split(","))
 
@@ -84,6 +91,24 @@ def main() -> int:
             srv = PolicyServer(cfg, params=eng.params, device=dev, backend="native")
             out["rollout"] = report(timed(lambda: srv.backtest(eng.prices), args.repeats), env_days)
             out["rollout_summary"] = benchkit.backtest_returns(eng)
+            if args.ledger:
+                from sharetrade.serve.rollout import ledger_from_trace
+
+                e = cfg.env
+
+                def trace_then_ledger():
+                    res = srv.backtest(eng.prices, trace=True)
+                    return ledger_from_trace(eng.prices, res.actions, history=H, budget0=e.budget, shares0=e.shares)
+
+                out["rollout_ledger"] = report(timed(lambda: srv.backtest(eng.prices, ledger=True), args.repeats),
+                                               env_days)
+                out["trace_only"] = report(timed(lambda: srv.backtest(eng.prices, trace=True), args.repeats), env_days)
+                out["trace_then_ledger"] = report(timed(trace_then_ledger, max(1, min(args.repeats, 2))), env_days)
+                a, b = srv.backtest(eng.prices), srv.backtest(eng.prices, ledger=True)
+                torch.cuda.synchronize()
+                assert torch.equal(a.final_portfolio.view(torch.int32), b.final_portfolio.view(torch.int32)), \
+                    "the ledger launch's final portfolios differ from the plain launch's"
+                out["ledger_final_portfolio_equal"] = True
         if "greedy" in what:
             res = {}
             out["greedy"] = report(timed(lambda: res.update(benchkit.greedy_episode_returns(eng)), args.repeats), env_days)

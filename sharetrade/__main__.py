@@ -40,7 +40,10 @@ def _cfg(a) -> Config:
 
 def _backtest(a, cfg: Config) -> dict:
     """``backtest``: the policy, buy-and-hold (Buy at every step, as benchkit.buy_and_hold_returns) and a uniform
-    random policy over the same series, each as mean / std / median of final portfolio - budget and trade counts."""
+    random policy over the same series, each as mean / std / median of final portfolio - budget and trade counts.
+    ``--report`` adds the risk report of each (drawdown, Sharpe, position, action mix, exposure / timing split,
+    position / price correlation and portfolio figures: ``BacktestResult.report``), ``--curve-out`` saves the
+    policy's portfolio curve; the policy's ledger rides along in its one launch."""
     import os
 
     import numpy as np
@@ -49,7 +52,7 @@ def _backtest(a, cfg: Config) -> dict:
     from .data import prices as dp
     from .serve import PolicyServer
     from .serve.http import load_checkpoint_params
-    from .serve.rollout import result_from, simulate_actions
+    from .serve.rollout import ledger_from_trace, result_from, simulate_actions
     from .trainer.engine import resolve_device
 
     if a.csv:
@@ -61,21 +64,29 @@ def _backtest(a, cfg: Config) -> dict:
     P = torch.from_numpy(np.ascontiguousarray(P, dtype=np.float32))
     params = load_checkpoint_params(a.ckpt, averaged=a.weights == "average") if a.ckpt else None
     srv = PolicyServer(cfg, params=params, device=resolve_device(a.device))
-    res = srv.backtest(P, trace=bool(a.trace_out))
+    res = srv.backtest(P, trace=bool(a.trace_out), ledger=bool(a.report or a.curve_out))
     e, H = cfg.env, cfg.model.history
     steps = res.steps
     g = torch.Generator().manual_seed(int(cfg.agent.seed))
-    base = {}
+    base, reports = {}, ({"policy": res.report()} if a.report else {})
     for name, acts in (("buy_and_hold", torch.zeros(P.shape[0], steps, dtype=torch.int8)),
                        ("uniform_random", torch.randint(0, 3, (P.shape[0], steps), generator=g).to(torch.int8))):
         out = simulate_actions(P, acts, history=H, budget0=e.budget, shares0=e.shares, compat=e.compat_decisions)
         base[name] = result_from(out, e.budget, 0, steps, False).summary()
+        if a.report:
+            led = ledger_from_trace(P, acts, history=H, budget0=e.budget, shares0=e.shares)
+            reports[name] = result_from(out, e.budget, 0, steps, False, led).report()
     if a.trace_out:
         os.makedirs(a.trace_out, exist_ok=True)
         np.save(os.path.join(a.trace_out, "actions.npy"), res.actions.cpu().numpy())
         np.save(os.path.join(a.trace_out, "equity.npy"), res.equity.cpu().numpy())
-    return {"series": int(P.shape[0]), "days": int(P.shape[1]), "steps": int(steps), "budget": float(e.budget),
-            "backend": srv.backend, "weights": (a.weights if a.ckpt else "init"), "policy": res.summary(), **base}
+    if a.curve_out:
+        np.save(a.curve_out, res.ledger.curve.cpu().numpy())
+    out = {"series": int(P.shape[0]), "days": int(P.shape[1]), "steps": int(steps), "budget": float(e.budget),
+           "backend": srv.backend, "weights": (a.weights if a.ckpt else "init"), "policy": res.summary(), **base}
+    for name, rep in reports.items():   # (--report: a `report` block in the policy's and every baseline's entry)
+        out[name] = {**out[name], "report": rep}
+    return out
 
 
 def _gru_path(a) -> bool:
@@ -334,10 +345,12 @@ def main(argv=None) -> int:
             p.add_argument("--ep-len", type=int, default=390, help="GRU policy: bars per episode")
             p.add_argument("--cost", type=float, default=0.01, help="GRU policy: cost per position change")
             p.add_argument("--report", action="store_true",
-                           help="GRU policy: add a `report` block (drawdown, Sharpe, hit rate, per-episode and "
-                                "portfolio figures) for the policy and every baseline")
+                           help="add a `report` block (drawdown, Sharpe and portfolio figures; GRU policy: hit rate "
+                                "and per-episode figures; MLP policy: position, action mix, exposure / timing) for "
+                                "the policy and every baseline")
             p.add_argument("--curve-out", default=None, metavar="F.npy",
-                           help="GRU policy: write the portfolio curve (per-bar sum of the series' rewards) here")
+                           help="write the portfolio curve here (GRU policy: per-bar sum of the series' rewards; MLP "
+                                "policy: per-day sum of the series' gains, float64)")
     a = ap.parse_args(argv)
     cfg = _cfg(a)
     logging.basicConfig(level=getattr(logging, cfg.log.loglevel, logging.INFO),

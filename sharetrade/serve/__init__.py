@@ -4,7 +4,8 @@
 * :class:`DynamicBatcher` — single requests from many client threads -> server batches;
 * :class:`PolicyServingActor` — the reference's actor message API over the server;
 * :meth:`PolicyServer.backtest` — whole episodes of a frozen policy in one launch (``csrc/qrollout.hip``,
-  :class:`RolloutKernel`, oracle :func:`reference_rollout`);
+  :class:`RolloutKernel`, oracle :func:`reference_rollout`), with the on-chip risk ledger (:class:`QLedger`,
+  oracle ``rollout.ledger_from_trace``) behind ``BacktestResult.report()``;
 * :class:`GruPolicy` — a frozen GRU(256) policy of config 5 and its backtest on minute bars
   (``csrc/gru_rollout.hip``, oracle :func:`reference_gru_rollout`), with the on-chip risk ledger
   (:class:`GruLedger`, oracle :func:`ledger_from_trace`) behind ``GruBacktestResult.report()``;
@@ -16,11 +17,11 @@ from .gru_rollout import (GruBacktestResult, GruLedger, GruPolicy, ledger_from_t
                           simulate_minute_actions)
 from .gru_serve import GruBatcher, GruDecision, GruSessionServer, reference_gru_serve
 from .kernel import ServeKernel, reference_select, supported
-from .rollout import BacktestResult, RolloutKernel, RolloutParams, reference_rollout
+from .rollout import BacktestResult, QLedger, RolloutKernel, RolloutParams, reference_rollout
 from .server import DynamicBatcher, PolicyServer
 
 __all__ = ["PolicyServer", "DynamicBatcher", "PolicyServingActor", "LoadPolicy", "PolicyLoaded", "ServeKernel",
-           "reference_select", "supported", "BacktestResult", "RolloutKernel", "RolloutParams", "reference_rollout",
+           "reference_select", "supported", "BacktestResult", "QLedger", "RolloutKernel", "RolloutParams", "reference_rollout",
            "GruPolicy", "GruBacktestResult", "GruLedger", "ledger_from_trace", "reference_gru_rollout",
            "simulate_minute_actions",
            "GruSessionServer", "GruBatcher", "GruDecision", "reference_gru_serve"]

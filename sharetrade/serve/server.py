@@ -142,13 +142,25 @@ class PolicyServer:
     # ---------------------------------------------------------------- backtesting
     def backtest(self, prices: ArrayLike, *, start: int = 0, steps: Optional[int] = None,
                  budget: Optional[ArrayLike] = None, shares: Optional[ArrayLike] = None, greedy: bool = True,
-                 trace: bool = False) -> R.BacktestResult:
+                 trace: bool = False, ledger: bool = False,
+                 ledger_state: Optional[torch.Tensor] = None) -> R.BacktestResult:
         """What the served policy does over price series [E, T] (or one series [T]): one decision and one
         trade per day from day ``start`` for ``steps`` days (default: to the end of the series), every env
         starting from the configured budget / shares or from ``budget`` / ``shares`` [E] (a continued
         episode).  ``greedy=False`` draws the epsilon-greedy policy of the config (ramp on the day).  The
-        native backend runs ``csrc/qrollout.hip`` (one launch); the torch backend the oracle on the CPU."""
+        native backend runs ``csrc/qrollout.hip`` (one launch); the torch backend the oracle on the CPU.
+
+        ``ledger``: also keep the risk ledger (``result.ledger``, a :class:`~sharetrade.serve.rollout.QLedger`, and
+        ``result.report()``): on the native backend the kernel's ledger instance in the same launch plus the
+        curve's reduction, on the torch backend ``ledger_from_trace`` on the oracle's actions.  ``ledger_state``
+        [E, 24] int32 is ``ledger.state`` of the piece before (pass that piece's ``budget`` / ``shares`` too).
+        Not with ``env.compat_decisions``, which trades from the initial holding every day."""
         c, m, a = self.cfg, self.cfg.model, self.cfg.agent
+        if ledger_state is not None and not ledger:
+            raise ValueError("ledger_state continues a ledger: pass ledger=True")
+        if ledger and c.env.compat_decisions:
+            raise ValueError("env.compat_decisions trades from the initial holding every day: it has no position "
+                             "ledger")
         P = torch.as_tensor(prices, dtype=torch.float32)
         if P.dim() == 1:
             P = P.view(1, -1)
@@ -175,14 +187,20 @@ class PolicyServer:
                 out = self._roll.run(Pd, start=int(start), steps=n,
                                      budget=None if b is None else b.to(self.device).contiguous(),
                                      shares=None if s is None else s.to(self.device).contiguous(),
-                                     greedy=greedy, trace=trace)
+                                     greedy=greedy, trace=trace, ledger=ledger,
+                                     ledger_state=None if ledger_state is None else
+                                     ledger_state.to(self.device, torch.int32).contiguous())
+                led = None
             else:
                 out = R.reference_rollout(self.params.cpu(), self.layout, P.cpu(), history=self.H,
                                           feat_mode=c.env.features, output_relu=m.output_relu,
                                           budget0=c.env.budget, shares0=c.env.shares, compat=c.env.compat_decisions,
                                           epsilon=math.inf if greedy else a.epsilon, ramp=a.ramp, key_seed=self.seed,
                                           start=int(start), steps=n, budget=b, shares=s)
-        return R.result_from(out, c.env.budget, start, n, trace)
+                led = R.ledger_from_trace(P.cpu(), out["actions"], history=self.H, budget0=c.env.budget,
+                                          shares0=c.env.shares, start=int(start), budget=b, shares=s,
+                                          ledger_state=ledger_state) if ledger else None
+        return R.result_from(out, c.env.budget, start, n, trace, led)
 
     def launch_into(self, x: torch.Tensor, acts: torch.Tensor, steps: Optional[torch.Tensor], seq: int,
                     q: Optional[torch.Tensor] = None) -> None:
