@@ -411,6 +411,8 @@ def _bind_batched():
         L.st_f32b_colsum_det.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]
         L.st_f32b_colsum_det.restype = C.c_int
+        L.st_f32b_colsum_part_floats.argtypes = [C.c_int, C.c_int]
+        L.st_f32b_colsum_part_floats.restype = C.c_longlong
         L._f32b_bound = True
     return L
 
